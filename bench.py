@@ -16,6 +16,13 @@ N > 1 (torchrun, one rank per GPU): the same 512^3 problem split into N
 boxes (z first: 2 -> 512x512x256 slabs, 4 -> 1x2x2, 8 -> 2x2x2), halo
 exchange by RCCL over xGMI: strong scaling.  Timing: barrier +
 device-synchronize on both sides of exactly K steps, max over ranks.
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR writes what the last timed step left (phi, the residual,
+the residual norms) as .npy files.  --full adds everything else this bench
+measures, each in runs of its own after the timed region: the smoother
+roofline (event-timed iterations, rocprofv3 --pmc traffic passes), the
+BiCGStab-bottom V-cycle, the CPU baselines and the final residual norm.
 """
 from __future__ import annotations
 
@@ -30,6 +37,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md: 8.0 TB/s)
 HBM_COPY_GBS = 6290.0  # measured float4 copy rate (MI355X_MICROARCH.md: ≈6.3 TB/s achievable)
+DUMP_LIMIT_BYTES = 48 * 10**6  # --dump-outputs: every file of every rank together
+DUMP_SEED = 20261019
 
 
 def parse():
@@ -40,6 +49,16 @@ def parse():
     ap.add_argument("--size", type=int, default=512, help="cells per side of the fine level")
     ap.add_argument("--levels", type=int, default=3)
     ap.add_argument("--nsmooth", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the smoother roofline (event-timed "
+                         "iterations, PMC traffic passes), the BiCGStab-bottom V-cycle, the CPU "
+                         "baselines and the final residual norm (the --no-* options below drop "
+                         "single parts of it); off: those fields of the result line are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one left -- phi, the residual "
+                         "and the timed steps' residual norms -- as DIR/<name>.npy (float64; at "
+                         f"most {DUMP_LIMIT_BYTES // 10**6} MB in all: fields too large for their "
+                         "share are sampled at fixed, seeded cells)")
     ap.add_argument("--no-fused", action="store_true", help="per-colour smoother launches")
     ap.add_argument("--boxes-per-rank", default="1,1,1",
                     help="split each rank's share into this many boxes (x,y,z) -- the multi-box "
@@ -158,6 +177,9 @@ def main():
     # queued (the GPU runs the next V-cycle's earlier part meanwhile) -- with
     # no instrumentation in the timed region
     elapsed, hist = timed(lambda: amg.iterations(fphi, frhs, fres, args.steps, norm_type=nt))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, grid, len(boxes), fphi, fres, hist, np)
+    full = args.full
 
     # the roofline: K more iterations with a HIP event pair around every
     # fine-level smoother relax (or launch) on the operator's stream
@@ -165,19 +187,19 @@ def main():
     launches = passes = 0
     smooth_ms = 0.0
     elapsed_ev = None
-    if not args.no_roofline_events:
+    if full and not args.no_roofline_events:
         mg.prof_smoother(True, fine_cells, per_relax=args.roofline_events == "relax")
         elapsed_ev, _ = timed(lambda: amg.iterations(fphi, frhs, fres, args.steps, norm_type=nt))
         launches, passes, smooth_ms = mg.prof_smoother_read()
         mg.prof_smoother(False)
-    r_final = amg.init_residual(fphi, frhs, fres, norm_type=0)
+    r_final = amg.init_residual(fphi, frhs, fres, norm_type=0) if full else None
 
     # the bottom solve reported separately ("+ bottom (report
     # separately)"): the same V-cycle with the reference's BiCGStab bottom
     # (Main_PoissonSolver.cpp:103-117) at the coarsest depth instead of
     # numMGsmooth GSRB sweeps, from phi = 0 on a second hierarchy
     bottom = None
-    if not args.no_bottom:
+    if full and not args.no_bottom:
         bottom = bottom_timing(mg, case, args, timed, nt, elapsed / args.steps)
 
     # dominant kernel: the fine-level smoother; passes_per_launch = 1 (one
@@ -200,7 +222,8 @@ def main():
         traffic = pmc_traffic(args)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_baseline_iters > 0:
+    if (full and rank == 0 and world == 1 and not args.no_cpu_baseline
+            and args.cpu_baseline_iters > 0):
         cpu = cpu_baseline(args, grid, fa, frhs, dom, dx, np)
     hb = traffic.get("hbm_bytes_per_launch") if traffic else None
 
@@ -213,6 +236,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "timed_region": "K AMRMultiGrid iterations, no instrumentation (the roofline's "
                             "event-timed iterations run after it, separately)",
@@ -267,7 +291,7 @@ def main():
                         "same workload; copy_rate_GBps = the measured float4 copy rate of "
                         "MI355X_MICROARCH.md (6.29 TB/s)",
                 "avg_launch_ms": round(avg_launch_ms, 5) if launches else None,
-                "timing": ("off" if args.no_roofline_events else
+                "timing": ("off" if not full or args.no_roofline_events else
                            "HIP events on the operator stream, one pair per relax call "
                            "(interval / launches), in K iterations timed after the headline's"
                            if args.roofline_events == "relax"
@@ -285,6 +309,31 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, grid, num_boxes, fphi, fres, hist, np):
+    """What a caller of the timed amg.iterations() holds after its last step:
+    phi, the residual r = rhs - L(phi) and the steps' residual norms, as
+    float64 .npy files.  One box on one rank: phi.npy, resid.npy; otherwise
+    every rank writes its own boxes as phi_box<global index>.npy.  A field
+    larger than its share of DUMP_LIMIT_BYTES is sampled at cells drawn by a
+    generator seeded with DUMP_SEED and the box's index (the same cells in
+    every run of the same arguments, and the same for phi and the residual)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_LIMIT_BYTES - 10**6) // (2 * num_boxes) // 8  # values per file
+    for i in range(grid.num_local):
+        gi = grid.boxes.index(tuple(grid.local_box(i)))
+        tag = "" if num_boxes == 1 else f"_box{gi}"
+        cells = None
+        for name, f in (("phi", fphi), ("resid", fres)):
+            a = f.download(i)
+            if a.size > share:
+                if cells is None:
+                    cells = np.random.default_rng([DUMP_SEED, gi]).integers(0, a.size, size=share)
+                a = a.reshape(-1)[cells]
+            np.save(os.path.join(out_dir, f"{name}{tag}.npy"), a)
+    if grid.comm.rank == 0:
+        np.save(os.path.join(out_dir, "residual_norms.npy"), np.asarray(hist, dtype=np.float64))
 
 
 def make_comm(mg, torch, dist, rank, world, transport):

@@ -12,7 +12,7 @@ for r in $(seq $ROUNDS); do
   for spec in ${VARIANTS}; do
     name=${spec%%:*}; envs=""
     [ "$spec" != "$name" ] && envs=${spec#*:} && envs=${envs//,/ }
-    env $envs timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-traffic \
+    env $envs timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-traffic \
       ${BENCH_ARGS:-} > gpurun_out/ab_env.tmp || exit $?
     python3 -c "import json; d=json.loads(open('gpurun_out/ab_env.tmp').read().strip().splitlines()[-1]); print(json.dumps({'variant':'$name','vcycles':d['value'],'ms':d['ms_per_step'],'launch_ms':d['roofline']['avg_launch_ms']}))" >> $out
   done

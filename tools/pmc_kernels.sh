@@ -9,7 +9,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 R=$(pwd); OUT=$R/gpurun_out/${PMC_OUT:-pmc_k}; mkdir -p $OUT
 KRE=${KRE:-k_restrict|k_prolong|k_residual|k_blas}
-BARGS=${BARGS:---steps 1 --warmup 0 --no-cpu-baseline}
+BARGS=${BARGS:---full --steps 1 --warmup 0 --no-cpu-baseline}
 CMD=${CMD:-$R/bench.py $BARGS}
 PASSES=${PASSES:-FETCH_SIZE;WRITE_SIZE;TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum;SQ_WAVES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES;SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU}
 IFS=';' read -r -a groups <<< "$PASSES"

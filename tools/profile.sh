@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 OUT=${OUT:-gpurun_out/prof}
 TAG=${TAG:-r01}
 KRE=${KRE:-k_gsrb}
-BARGS=${BARGS:---steps 5 --warmup 1 --no-cpu-baseline}
+BARGS=${BARGS:---full --steps 5 --warmup 1 --no-cpu-baseline}
 mkdir -p "$OUT"
 R=$(pwd)
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$R/$OUT/trace" -o "$TAG" --output-format csv -- python3 "$R/bench.py" $BARGS > "$OUT/trace.log" 2>&1

@@ -6,8 +6,8 @@
 # Steps:
 #   tests        pytest -m gpu (PYTEST_K: a -k expression; PYTEST_ARGS: more options)
 #   smoke        __graft_entry__.smoke()
-#   bench        the default bench.py line (BENCH_ARGS appended)
-#   benchq       bench.py without the CPU baseline / PMC passes (BENCH_ARGS)
+#   bench        the bench.py --full line (BENCH_ARGS appended)
+#   benchq       bench.py --full without the CPU baseline / PMC passes (BENCH_ARGS)
 #   bottom       tools/bench_bottom.py (BOTTOM_ARGS); BOTTOM_ENVS="A=1 B=2,A=0" runs
 #                one line per comma-separated env set, interleaved BOTTOM_REPS times
 #   ab           bench.py interleaved over AB_ENVS ("X=1,X=0"), AB_REPS rounds (BENCH_ARGS)
@@ -50,7 +50,7 @@ trace_sum() {  # trace_sum DIR NAME
   rm -rf "$1"
   sed -n 1,25p "$O/$2.txt"
 }
-BQ="--no-cpu-baseline --no-traffic"
+BQ="--full --no-cpu-baseline --no-traffic"
 for s in ${STEPS:-tests smoke bench}; do
   case $s in
     tests) if [ -n "${PYTEST_K:-}" ]; then
@@ -59,7 +59,7 @@ for s in ${STEPS:-tests smoke bench}; do
              run tests 1100 $PYT tests -m gpu ${PYTEST_ARGS:-} || exit $?
            fi ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
-    bench) run bench 900 python bench.py ${BENCH_ARGS:-} || exit $?
+    bench) run bench 900 python bench.py --full ${BENCH_ARGS:-} || exit $?
            tail -n 1 "$O/bench.log" > "$O/bench_line.json" ;;
     benchq) run benchq 600 python bench.py $BQ ${BENCH_ARGS:-} || exit $?
             tail -n 1 "$O/benchq.log" > "$O/benchq_line.json" ;;
