@@ -261,6 +261,8 @@ MGIC_API int mgic_op_norm(mgic_op op, mgic_field x, int ord, double *out);
 /* BiCGStabSolver<LevelData>::solve with this op (bottom solver) */
 MGIC_API int mgic_op_bicgstab(mgic_op op, mgic_field phi, mgic_field rhs, int homogeneous,
                               const mgic_mg_params *p, int *iterations);
+/* whether the calling thread's last mgic_op_bicgstab ran its loop on the device */
+MGIC_API int mgic_op_bicgstab_info(int *device);
 
 /* ---- multigrid (AMRMultiGrid on one AMR level + MultiGrid hierarchy) */
 MGIC_API int mgic_mg_create(mgic_factory f, const mgic_mg_params *p, mgic_mg *out);

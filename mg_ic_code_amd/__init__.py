@@ -20,6 +20,7 @@ from .core import (  # noqa: F401
     VariableCoeffPoissonOperator,
     VariableCoeffPoissonOperatorFactory,
     bicgstab,
+    bicgstab_on_device,
     defineOperatorFactory,
     device_synchronize,
     prof_smoother,

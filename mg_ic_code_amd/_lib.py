@@ -158,6 +158,7 @@ SIGNATURES = {
     "mgic_op_dot": [H, H, H, PD],
     "mgic_op_norm": [H, H, c_int, PD],
     "mgic_op_bicgstab": [H, H, H, c_int, POINTER(MGParams), PI],
+    "mgic_op_bicgstab_info": [PI],
     "mgic_mg_create": [H, POINTER(MGParams), PH],
     "mgic_mg_destroy": [H],
     "mgic_mg_num_depths": [H, PI],

@@ -44,6 +44,7 @@ __all__ = [
     "BiCGStabSolver",
     "defineOperatorFactory",
     "bicgstab",
+    "bicgstab_on_device",
     "set_binary_bh_coefs",
     "set_nl_coefs",
     "prof_smoother",
@@ -555,6 +556,13 @@ def bicgstab(op: VariableCoeffPoissonOperator, phi: LevelData, rhs: LevelData,
     call("mgic_op_bicgstab", op.handle, phi.handle, rhs.handle, int(bool(homogeneous)),
          ctypes.byref(p), ctypes.byref(it))
     return it.value
+
+
+def bicgstab_on_device() -> bool:
+    """Whether this thread's last :func:`bicgstab` ran its loop on the device."""
+    dv = ctypes.c_int()
+    call("mgic_op_bicgstab_info", ctypes.byref(dv))
+    return bool(dv.value)
 
 
 class AMRMultiGrid:

@@ -925,6 +925,8 @@ MGIC_API int mgic_op_dot(mgic_op op, mgic_field x, mgic_field y, double *out) {
 MGIC_API int mgic_op_norm(mgic_op op, mgic_field x, int ord, double *out) {
   OPGUARD(NEED(x); NEED(out); *out = o.norm(*x->f, ord));
 }
+static thread_local int op_bicgstab_device = 0;  // the last mgic_op_bicgstab of this thread
+
 MGIC_API int mgic_op_bicgstab(mgic_op op, mgic_field phi, mgic_field rhs, int h,
                               const mgic_mg_params *p, int *iters) {
   OPGUARD({
@@ -933,7 +935,15 @@ MGIC_API int mgic_op_bicgstab(mgic_op op, mgic_field phi, mgic_field rhs, int h,
     BiCGStabSolver s;
     s.prm = to_mg(p).bicg;
     const int it = s.solve(o, *phi->f, *rhs->f, h != 0);
+    op_bicgstab_device = s.last_device ? 1 : 0;
     if (iters) *iters = it;
+  });
+}
+
+MGIC_API int mgic_op_bicgstab_info(int *device) {
+  return guard([&] {
+    NEED(device);
+    *device = op_bicgstab_device;
   });
 }
 

@@ -1197,7 +1197,12 @@ int BiCGStabSolver::solveDevice(VariableCoeffPoissonOperator &op, LevelData &phi
       t1 = t2;
       t2 = batch();
     }
-    h = *dw.h_pub;  // frozen once done: later batches skip and publish the same words
+    // t2's publish may still be storing its words: a stop inside t2 would
+    // show done = 1 beside t1's reason / epend.  Once the last queued batch
+    // has published nothing is in flight; the state is frozen after a stop,
+    // so these are the stop's own words (t2's launches return at once)
+    wait(t2);
+    h = *dw.h_pub;
     if (h.epend) op.incr(E, PT, h.alpha);  // the stop came after S = R - alpha V
     if (h.reason != kern::kBicgRestart) break;
     ++h.restarts;  // |m| <= small |rho1|: restart (solve()'s else branch)

@@ -96,6 +96,7 @@ _sig = {
     "orc_mg_norm": [ctypes.c_void_p, c_int, c_int, c_int],
     "orc_mg_dot": [ctypes.c_void_p, c_int, c_int, c_int],
     "orc_mg_last_bicg_iters": [ctypes.c_void_p],
+    "orc_mg_last_bicg_restarts": [ctypes.c_void_p, PI],
     "orc_binary_bh_coefs": [POINTER(BHParams), PI, PI, c_double, POINTER(c_double), POINTER(c_double)],
     "orc_nl_coefs": [POINTER(BHParams), PI, PI, c_double, POINTER(c_double), POINTER(c_double),
                      POINTER(c_double)],
@@ -114,7 +115,8 @@ for _n, _a in _sig.items():
     _f = getattr(_lib, _n)
     _f.argtypes = _a
     _f.restype = _res.get(_n, c_int if _n in ("orc_mg_nlevels", "orc_mg_bicgstab",
-                                               "orc_mg_last_bicg_iters", "orc_get_threads",
+                                               "orc_mg_last_bicg_iters", "orc_mg_last_bicg_restarts",
+                                               "orc_get_threads",
                                                "orc_pin_threads")
                           else None)
 _lib.orc_mg_solve.restype = c_int
@@ -375,6 +377,16 @@ class OracleMG:
         it = _lib.orc_mg_solve(self._h, int(mg_iters), int(imax), float(eps), int(norm_type),
                                ctypes.byref(out))
         return it, out.value
+
+    def last_bicg_iters(self) -> int:
+        """Iterations of the last BiCGStab solve (bottom, direct or outer)."""
+        return _lib.orc_mg_last_bicg_iters(self._h)
+
+    def last_bicg_restarts(self):
+        """(restarts the last BiCGStab solve took, whether it ended on the limit)."""
+        lim = c_int()
+        n = _lib.orc_mg_last_bicg_restarts(self._h, ctypes.byref(lim))
+        return n, bool(lim.value)
 
     def norm(self, level, field, norm_type=2) -> float:
         return _lib.orc_mg_norm(self._h, level, field, int(norm_type))

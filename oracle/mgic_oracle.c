@@ -266,6 +266,7 @@ struct orc_mg {
   int nlev;
   orc_level *lev;
   int last_iters;
+  int last_restarts, last_hit_limit; /* of the last BiCGStab solve */
 };
 
 static const int *vb(const orc_level *L, int b) { return L->vbox + 6 * b; }
@@ -355,6 +356,10 @@ void orc_mg_destroy(orc_mg *mg) {
 
 int orc_mg_nlevels(const orc_mg *mg) { return mg->nlev; }
 int orc_mg_last_bicg_iters(const orc_mg *mg) { return mg->last_iters; }
+int orc_mg_last_bicg_restarts(const orc_mg *mg, int *hit_limit) {
+  if (hit_limit) *hit_limit = mg->last_hit_limit;
+  return mg->last_restarts;
+}
 double orc_mg_dx(const orc_mg *mg, int level) { return mg->lev[level].dx; }
 void orc_mg_box(const orc_mg *mg, int level, int box, int *lohi) {
   memcpy(lohi, mg->lev[level].vbox + 6 * box, 6 * sizeof(int));
@@ -710,7 +715,7 @@ static int bicgstab_core(orc_mg *mg, int l, int fe, int fr, int hom, const bicg_
   double rho1 = 0.0, rho2 = 0.0, alpha = 0.0, beta = 0.0, omega = 0.0;
   const double init_norm = orc_mg_norm(mg, l, W_R, nt);
   double nrm = init_norm;
-  int it = 0, init = 1, restarts = 0;
+  int it = 0, init = 1, restarts = 0, hit_limit = 0;
   while (it < p->imax && nrm > p->eps * init_norm && nrm > p->reps) {
     ++it;
     rho2 = rho1;
@@ -749,7 +754,10 @@ static int bicgstab_core(orc_mg *mg, int l, int fe, int fr, int hom, const bicg_
       nrm = orc_mg_norm(mg, l, W_R, nt);
       if (omega == 0.0) break;
     } else {
-      if (restarts >= p->restarts) break;
+      if (restarts >= p->restarts) {
+        hit_limit = 1;
+        break;
+      }
       ++restarts;
       lv_op(mg, l, fe, W_E, 1.0, 1);
       orc_mg_residual(mg, l, W_R, fe, fr, hom);
@@ -761,6 +769,8 @@ static int bicgstab_core(orc_mg *mg, int l, int fe, int fr, int hom, const bicg_
   }
   lv_op(mg, l, fe, W_E, 1.0, 1);
   mg->last_iters = it;
+  mg->last_restarts = restarts;
+  mg->last_hit_limit = hit_limit;
   return it;
 }
 

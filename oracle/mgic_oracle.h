@@ -155,6 +155,9 @@ int orc_mg_solve(orc_mg *mg, int mg_iters, int imax, double eps, int norm_type,
 double orc_mg_norm(orc_mg *mg, int level, int field, int norm_type);
 double orc_mg_dot(orc_mg *mg, int level, int fx, int fy);
 int orc_mg_last_bicg_iters(const orc_mg *mg);
+/* restarts (|m| <= small |rho|) the last BiCGStab solve took; *hit_limit = 1
+ * when it ended because none were left */
+int orc_mg_last_bicg_restarts(const orc_mg *mg, int *hit_limit);
 
 /* ---- input generator (SetLevelData.cpp / SetBinaryBH.H / MyPhiFunction.H) */
 typedef struct {

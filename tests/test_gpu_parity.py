@@ -464,8 +464,18 @@ def test_bicgstab_bottom_on_device_bitwise(comm, monkeypatch, n, nlevels):
         assert r[0] == runs[0][0]
         assert r[1] == runs[0][1]
         assert np.array_equal(r[2], runs[0][2])
-    # (the 8^3 bottom converges in one iteration, then starts converged)
-    assert max(runs[0][1]) >= (8 if n == 128 else 1), runs[0][1]
+    # What each row is (the oracle's counts for the same inputs): only the
+    # 128^3 row iterates.  alpha = 1 with random aCoef is diagonally dominant:
+    # the 8^3 bottom takes 1, 0, 0 iterations (it then starts converged), the
+    # 16^3 one 1, 1, 1 and the 32^3 one 2, 2, 2 -- stop tests and batching, not
+    # Krylov solves.  The 64^3 Poisson bottom takes 51, 47, 38; its counts move
+    # with the reduction order (49, 48, 37 on another decomposition), so it is
+    # pinned here only, host against device.  The iterating bottoms that are
+    # compared with the oracle are in tests/test_bicgstab_parity.py.
+    if n == 128:
+        assert min(runs[0][1]) >= 30, runs[0][1]
+    else:
+        assert 1 <= max(runs[0][1]) <= 2, runs[0][1]
 
 
 def test_bicgstab_bottom_replay_is_repeatable(comm):
