@@ -258,6 +258,15 @@ MGIC_API int mgic_op_axby(mgic_op op, mgic_field lhs, mgic_field x, mgic_field y
 MGIC_API int mgic_op_scale(mgic_op op, mgic_field lhs, double s);
 MGIC_API int mgic_op_dot(mgic_op op, mgic_field x, mgic_field y, double *out);
 MGIC_API int mgic_op_norm(mgic_op op, mgic_field x, int ord, double *out);
+/* BiCGStab's fused updates (the host loop's; each equals the separate passes
+ * bit for bit).  s = r + ca v; e = e + cb pt; *out = norm(s, ord), ord 0/1/2 */
+MGIC_API int mgic_op_axpy2_norm(mgic_op op, mgic_field s, mgic_field r, mgic_field v, double ca,
+                                mgic_field e, mgic_field pt, double cb, int ord, double *out);
+/* *ts = dot(t, s), *tt = dot(t, t) in one pass */
+MGIC_API int mgic_op_dot2(mgic_op op, mgic_field t, mgic_field s, double *ts, double *tt);
+/* p = ((p * beta) + c v) + 1.0 r */
+MGIC_API int mgic_op_bicg_p(mgic_op op, mgic_field p, mgic_field v, mgic_field r, double beta,
+                            double c);
 /* BiCGStabSolver<LevelData>::solve with this op (bottom solver) */
 MGIC_API int mgic_op_bicgstab(mgic_op op, mgic_field phi, mgic_field rhs, int homogeneous,
                               const mgic_mg_params *p, int *iterations);

@@ -157,6 +157,9 @@ SIGNATURES = {
     "mgic_op_scale": [H, H, c_double],
     "mgic_op_dot": [H, H, H, PD],
     "mgic_op_norm": [H, H, c_int, PD],
+    "mgic_op_axpy2_norm": [H, H, H, H, c_double, H, H, c_double, c_int, PD],
+    "mgic_op_dot2": [H, H, H, PD, PD],
+    "mgic_op_bicg_p": [H, H, H, H, c_double, c_double],
     "mgic_op_bicgstab": [H, H, H, c_int, POINTER(MGParams), PI],
     "mgic_op_bicgstab_info": [PI],
     "mgic_mg_create": [H, POINTER(MGParams), PH],

@@ -484,6 +484,26 @@ class VariableCoeffPoissonOperator:
         call("mgic_op_norm", self._h, x.handle, int(ord), ctypes.byref(out))
         return out.value
 
+    # --- BiCGStab's fused updates (the host loop's)
+    def axpy2Norm(self, s: LevelData, r: LevelData, v: LevelData, ca: float, e: LevelData,
+                  pt: LevelData, cb: float, ord: int = 2) -> float:
+        """s = r + ca v; e = e + cb pt; returns norm(s, ord)."""
+        out = ctypes.c_double()
+        call("mgic_op_axpy2_norm", self._h, s.handle, r.handle, v.handle, ctypes.c_double(ca),
+             e.handle, pt.handle, ctypes.c_double(cb), int(ord), ctypes.byref(out))
+        return out.value
+
+    def dot2(self, t: LevelData, s: LevelData) -> Tuple[float, float]:
+        """(dot(t, s), dot(t, t)) in one pass."""
+        ts, tt = ctypes.c_double(), ctypes.c_double()
+        call("mgic_op_dot2", self._h, t.handle, s.handle, ctypes.byref(ts), ctypes.byref(tt))
+        return ts.value, tt.value
+
+    def bicgP(self, p: LevelData, v: LevelData, r: LevelData, beta: float, c: float):
+        """p = ((p * beta) + c v) + 1.0 r."""
+        call("mgic_op_bicg_p", self._h, p.handle, v.handle, r.handle, ctypes.c_double(beta),
+             ctypes.c_double(c))
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h:

@@ -925,6 +925,19 @@ MGIC_API int mgic_op_dot(mgic_op op, mgic_field x, mgic_field y, double *out) {
 MGIC_API int mgic_op_norm(mgic_op op, mgic_field x, int ord, double *out) {
   OPGUARD(NEED(x); NEED(out); *out = o.norm(*x->f, ord));
 }
+MGIC_API int mgic_op_axpy2_norm(mgic_op op, mgic_field s, mgic_field r, mgic_field v, double ca,
+                                mgic_field e, mgic_field pt, double cb, int ord, double *out) {
+  OPGUARD(NEED(s); NEED(r); NEED(v); NEED(e); NEED(pt); NEED(out);
+          MGIC_CHECK(ord >= 0 && ord <= 2, "axpy2_norm: ord is 0, 1 or 2");
+          *out = o.axpy2Norm(*s->f, *r->f, *v->f, ca, *e->f, *pt->f, cb, ord));
+}
+MGIC_API int mgic_op_dot2(mgic_op op, mgic_field t, mgic_field s, double *ts, double *tt) {
+  OPGUARD(NEED(t); NEED(s); NEED(ts); NEED(tt); o.dot2(*t->f, *s->f, *ts, *tt));
+}
+MGIC_API int mgic_op_bicg_p(mgic_op op, mgic_field p, mgic_field v, mgic_field r, double beta,
+                            double c) {
+  OPGUARD(NEED(p); NEED(v); NEED(r); o.bicgP(*p->f, *v->f, *r->f, beta, c));
+}
 static thread_local int op_bicgstab_device = 0;  // the last mgic_op_bicgstab of this thread
 
 MGIC_API int mgic_op_bicgstab(mgic_op op, mgic_field phi, mgic_field rhs, int h,

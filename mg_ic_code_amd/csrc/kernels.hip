@@ -26,10 +26,17 @@ __device__ __forceinline__ T ghost_of(int mode, T c, T near) {
   return mode == kBcDirichlet ? (c - near) : (mode == kBcNeumannHom ? near : near + c);
 }
 
-// reduction operator: sums (KIND < 3) and maxima (KIND >= 3, also of |x|)
+// reduction operator: sums (KIND < 3) and maxima (KIND >= 3, also of |x|);
+// a is the running value, b the term (or another running value).
+// NaN terms: max|x| (KIND 3) keeps the running value, which is the oracle's
+// statement (orc_mg_norm: s = a > s ? a : s), so it never turns NaN and the
+// position of a NaN cannot change the result (for NaN-free data the bits
+// of a > b ? a : b: |x| is never -0).  max x / max -x (KIND 4, 5) never
+// meet a NaN: red_term turns it into +inf.
 template <int KIND>
 __device__ __forceinline__ double red_op(double a, double b) {
-  if constexpr (KIND >= 3) return a > b ? a : b;
+  if constexpr (KIND == 3) return b > a ? b : a;
+  else if constexpr (KIND >= 4) return a > b ? a : b;
   else return a + b;
 }
 
@@ -848,8 +855,12 @@ __device__ __forceinline__ double red_term(const double *__restrict__ x,
   const double v = x[idx];
   if constexpr (KIND == 0) return v * y[idx];
   else if constexpr (KIND == 2) return v * v;
-  else if constexpr (KIND == 4) return v;
-  else if constexpr (KIND == 5) return -v;
+  // max x / max -x feed the host's constant-bCoef and lambda-range tests
+  // (resetLambda), which a NaN must fail on every rank: it counts as +inf in
+  // both, so max != min and neither is finite, whatever a transport's max
+  // does with a NaN
+  else if constexpr (KIND == 4) return v != v ? __builtin_huge_val() : v;
+  else if constexpr (KIND == 5) return v != v ? __builtin_huge_val() : -v;
   else return fabs(v);
 }
 

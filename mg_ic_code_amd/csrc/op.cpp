@@ -316,7 +316,9 @@ void VariableCoeffPoissonOperator::resetLambda() {
   // a gathered depth on a rank that does not hold it: nothing to compute
   // (it never runs a kernel or a reduction there)
   if (owner_local >= 0 && grid->comm->rank() != owner_local) return;
-  // is bCoef one value everywhere?  (max b == min b over all ranks' boxes)
+  // is bCoef one value everywhere?  (max b == min b over all ranks' boxes; a
+  // NaN cell counts as +inf in both reductions -- kernels.hip: red_term -- so
+  // bmax = +inf, bmin = -inf: never constant, and a lambda never in range)
   const double bmax = reduce(4, *m_bCoef, nullptr), bmin = -reduce(5, *m_bCoef, nullptr);
   b_const_ = bmax == bmin && std::isfinite(bmax);
   b_val_ = b_const_ ? bmax : 1.0;

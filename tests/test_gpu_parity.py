@@ -15,6 +15,7 @@ import pytest
 
 import oracle
 from oracle import Fab
+from tests import reduce_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -224,10 +225,18 @@ def test_operator_methods_bitwise(comm, rng, parts):
     q = n // 4
     assert np.array_equal(download_global(op2.m_aCoef, op2.grid, (q, q, q)), o.get(2, oracle.ACOEF, 0))
     assert np.array_equal(download_global(op2.m_bCoef, op2.grid, (q, q, q)), o.get(2, oracle.BCOEF, 0))
-    # norms / dots agree to rounding (parallel reduction order)
+    # norms / dots: equal to the reduction's stated order bit for bit and
+    # within that order's error bound of the exact sums (tests/reduce_ref.py);
+    # the oracle sums cell after cell, so it agrees to rounding
+    nloc = range(grid.num_local)
+    reduce_ref.assert_level_reductions(op, fu, S["frhs"], [fu.download(b) for b in nloc],
+                                       [S["frhs"].download(b) for b in nloc])
     d_g = op.dotProduct(fu, S["frhs"])
     d_o = o.dot(0, oracle.PHI, oracle.RHS)
     assert abs(d_g - d_o) <= 1e-12 * abs(d_o)
+    for ord in (1, 2):
+        n_o = o.norm(0, oracle.PHI, ord)
+        assert abs(op.norm(fu, ord) - n_o) <= 1e-12 * n_o
     assert op.norm(fu, 0) == o.norm(0, oracle.PHI, 0)
 
 
