@@ -210,6 +210,52 @@ MGIC_API int mgic_field_nl_coefs(mgic_field psi, mgic_field acoef, mgic_field rh
 /* set_constant_K_integrand (SetLevelData.cpp:131-180) at psi (NULL: 1):
  * the integrand of the periodic integrability condition for K */
 MGIC_API int mgic_field_nl_integrand(mgic_field psi, mgic_field out, const double bh[13]);
+
+/* ---- set_grids (SetGrids.cpp:31-149): the AMR hierarchy from tagging.
+ * The condition and the tags are device kernels; clustering, nesting and the
+ * owners are host integer code (no device is touched by mgic_regrid_*). */
+/* set_regrid_condition (SetLevelData.cpp:190-240) at psi (NULL: 1, what
+ * set_grids uses); no ghost cell of psi is read */
+MGIC_API int mgic_field_regrid_condition(mgic_field psi, mgic_field out, const double bh[13]);
+/* norm(x, ord) of one level over every rank (ord 0 max, 1 sum |x|, 2 root of
+ * sum x^2): mgic_op_norm's exact level reduction, for a field that has no
+ * operator (set_tag_cells' maxRHS, SetGrids.cpp:184) */
+MGIC_API int mgic_field_norm(mgic_field x, int ord, double *out);
+/* set_tag_cells (SetGrids.cpp:172-207) onto the clustering lattice of spacing
+ * c level cells (lattice index = floor(cell / c)): a cell is tagged iff
+ * |cond| >= tag_val; tags grown by `grow` cells and clipped to the domain
+ * box set every lattice cell they reach.  The mask covers the lattice
+ * bounding box of the level: all of its boxes (every rank's), grown by
+ * `grow`, clipped to the domain, rounded out to whole lattice cells.
+ * lat_lo / lat_n (always written): its low corner and extents in lattice
+ * cells.  mask_host == NULL: the size query.  Otherwise mask_host receives
+ * lat_n[0]*lat_n[1]*lat_n[2] bytes (x fastest), 1 where THIS rank's cells
+ * set a lattice cell; the call synchronises. */
+MGIC_API int mgic_field_tag_lattice(mgic_field cond, double tag_val, int grow, int c,
+                                    int lat_lo[3], int lat_n[3], unsigned char *mask_host);
+/* c = max(block_factor / 2, 1), maxlen = max(max_grid_size / block_factor, 1);
+ * MGIC_EBADARG unless block_factor is a power of two */
+MGIC_API int mgic_regrid_lattice(int block_factor, int max_grid_size, int *c, int *maxlen);
+/* Berger-Rigoutsos clustering of a byte mask (n[0] fastest) into disjoint
+ * boxes in mask indices, at most maxlen a side, sorted by (lo_z, lo_y, lo_x).
+ * *nbox = their number; the first min(cap, *nbox) are written to boxes
+ * (6 ints each; cap = 0: count only). */
+MGIC_API int mgic_regrid_cluster(const unsigned char *mask, const int n[3], double fill_ratio,
+                                 int maxlen, int cap, int *nbox, int *boxes);
+/* BRMeshRefine::regrid stand-in, top-down with proper nesting: the tag
+ * lattices of levels 0 .. nlev-1 (masks[l] over lattice cells lat_lo[3l..] +
+ * [0, lat_n[3l..])) -> the boxes of levels 1 .. nlev.  nbox[l] = the number
+ * of boxes of level l + 1; boxes = the lists concatenated (cap as above);
+ * *new_finest = the highest level with boxes.  MGIC_EBADARG when
+ * block_factor is not a power of two or a level's domain is not a multiple
+ * of the lattice spacing. */
+MGIC_API int mgic_regrid_levels(int nlev, const int domain0[6], const unsigned char *const *masks,
+                                const int *lat_lo, const int *lat_n, int block_factor,
+                                int max_grid_size, double fill_ratio, int nesting_radius, int cap,
+                                int *nbox, int *boxes, int *new_finest);
+/* LoadBalance stand-in: box i of the sorted list goes to rank
+ * floor(size * (prefix_i + cells_i / 2) / total) */
+MGIC_API int mgic_regrid_owners(int nbox, const int *boxes, int size, int *owners);
 /* every cell of the allocation, ghosts included (set_initial_conditions
  * sets psi over the whole FAB, SetLevelData.cpp:31-72) */
 MGIC_API int mgic_field_set_val_all(mgic_field f, double v);

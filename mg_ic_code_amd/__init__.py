@@ -29,6 +29,7 @@ from .core import (  # noqa: F401
     set_nl_coefs,
     set_device,
 )
+from .grids import set_grids  # noqa: F401
 from ._lib import IO_LIB_PATH, LIB_PATH, lib  # noqa: F401
 from .output import output_final_data, output_solver_data  # noqa: F401
 

@@ -107,6 +107,14 @@ SIGNATURES = {
     "mgic_field_nl_coefs": [H, H, H, PD],
     "mgic_field_nl_integrand": [H, H, PD],
     "mgic_field_set_val_all": [H, c_double],
+    "mgic_field_regrid_condition": [H, H, PD],
+    "mgic_field_norm": [H, c_int, PD],
+    "mgic_field_tag_lattice": [H, c_double, c_int, c_int, PI, PI, c_void_p],
+    "mgic_regrid_lattice": [c_int, c_int, PI, PI],
+    "mgic_regrid_cluster": [c_void_p, PI, c_double, c_int, c_int, PI, PI],
+    "mgic_regrid_levels": [c_int, PI, POINTER(c_void_p), PI, PI, c_int, c_int, c_double, c_int,
+                           c_int, PI, PI, PI],
+    "mgic_regrid_owners": [c_int, PI, c_int, PI],
     "mgic_op_update_psi": [H, H, H],
     "mgic_plan_create": [c_int, c_int, PI, PI, c_int, PI, PI, c_int, PI, PI, c_int, c_int, PH],
     "mgic_plan_create_shell": [c_int, c_int, PI, PI, c_int, PI, PI, c_int, PH],

@@ -1,4 +1,5 @@
 // capi.cpp -- extern "C" boundary (include/mgic.h) over the C++ layer.
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -8,6 +9,7 @@
 #include "amr.hpp"
 #include "mixed.hpp"
 #include "op.hpp"
+#include "regrid.hpp"
 
 using namespace mgic;
 
@@ -699,6 +701,150 @@ MGIC_API int mgic_field_grchombo_vars(mgic_field psi, int n, int k0, int nk, con
 MGIC_API int mgic_field_solver_vars(mgic_field dpsi, mgic_field rhs, mgic_field psi, int n, int k0,
                                     int nk, const double bh[13], double *out, int out_on_device) {
   return guard([&] { output_vars_capi(1, psi, dpsi, rhs, n, k0, nk, bh, out, out_on_device); });
+}
+// ---- set_grids (SetGrids.cpp:31-149): condition and tags on
+// the device, clustering on the host (regrid.cpp)
+MGIC_API int mgic_field_regrid_condition(mgic_field psi, mgic_field out, const double bh[13]) {
+  return guard([&] {
+    NEED(out);
+    NEED(bh);
+    const Grid &g = *out->f->grid;
+    if (psi) check_same_layout(g, *psi->f, "psi");
+    const kern::BhParams p = bh_params(bh);
+    for (int n = 0; n < g.nlocal(); ++n)
+      kern::regrid_condition(out->f->p[n], psi ? psi->f->p[n] : nullptr, g.box_args_plain(n), g.dx,
+                             p, g.comm->stream());
+  });
+}
+MGIC_API int mgic_field_norm(mgic_field x, int ord, double *out) {
+  return guard([&] {
+    NEED(x);
+    NEED(out);
+    MGIC_CHECK(ord >= 0 && ord <= 2, "ord must be 0, 1 or 2");
+    VariableCoeffPoissonOperator op;  // the layout alone: no coefficients, no plans
+    op.define(x->f->grid, OpParams());
+    *out = op.norm(*x->f, ord);
+  });
+}
+MGIC_API int mgic_field_tag_lattice(mgic_field cond, double tag_val, int grow, int c,
+                                    int lat_lo[3], int lat_n[3], unsigned char *mask_host) {
+  return guard([&] {
+    NEED(cond);
+    NEED(lat_lo);
+    NEED(lat_n);
+    MGIC_CHECK(grow >= 0 && grow <= (1 << 20), "grow must be >= 0");
+    MGIC_CHECK(c >= 1, "lattice spacing must be >= 1");
+    const Grid &g = *cond->f->grid;
+    MGIC_CHECK(!g.boxes.empty(), "the level has no boxes");
+    // the lattice bounding box: every box of the level (all ranks), grown and
+    // clipped to the domain, in lattice cells
+    long cells = 1;
+    for (int d = 0; d < 3; ++d) {
+      int lo = g.boxes[0].lo[d], hi = g.boxes[0].hi[d];
+      for (const Box &b : g.boxes) {
+        lo = std::min(lo, b.lo[d]);
+        hi = std::max(hi, b.hi[d]);
+      }
+      lo = std::max(lo - grow, g.domain.lo[d]);
+      hi = std::min(hi + grow, g.domain.hi[d]);
+      lat_lo[d] = floordiv(lo, c);
+      lat_n[d] = floordiv(hi, c) - lat_lo[d] + 1;
+      cells *= lat_n[d];
+    }
+    if (!mask_host) return;  // the size query
+    const hipStream_t st = g.comm->stream();
+    unsigned char *d = static_cast<unsigned char *>(scratch_device((size_t)cells));
+    MGIC_HIP(hipMemsetAsync(d, 0, (size_t)cells, st));
+    for (int n = 0; n < g.nlocal(); ++n)
+      kern::tag_lattice(d, cond->f->p[n], g.box_args_plain(n), tag_val, grow, c, g.domain.lo,
+                        g.domain.hi, lat_lo, lat_n, st);
+    MGIC_HIP(hipMemcpyAsync(mask_host, d, (size_t)cells, hipMemcpyDeviceToHost, st));
+    MGIC_HIP(hipStreamSynchronize(st));
+  });
+}
+static std::vector<regrid::IBox> to_iboxes(int nbox, const int *boxes) {
+  std::vector<regrid::IBox> v((size_t)nbox);
+  for (int i = 0; i < nbox; ++i)
+    for (int d = 0; d < 3; ++d) {
+      v[i].lo[d] = boxes[6 * i + d];
+      v[i].hi[d] = boxes[6 * i + 3 + d];
+    }
+  return v;
+}
+static void from_iboxes(const std::vector<regrid::IBox> &v, int cap, int *boxes) {
+  for (int i = 0; i < (int)v.size() && i < cap; ++i)
+    for (int d = 0; d < 3; ++d) {
+      boxes[6 * i + d] = v[i].lo[d];
+      boxes[6 * i + 3 + d] = v[i].hi[d];
+    }
+}
+MGIC_API int mgic_regrid_lattice(int block_factor, int max_grid_size, int *c, int *maxlen) {
+  return guard([&] {
+    NEED(c);
+    NEED(maxlen);
+    std::string err;
+    MGIC_CHECK(regrid::lattice_params(block_factor, max_grid_size, c, maxlen, &err), err);
+  });
+}
+MGIC_API int mgic_regrid_cluster(const unsigned char *mask, const int n[3], double fill_ratio,
+                                 int maxlen, int cap, int *nbox, int *boxes) {
+  return guard([&] {
+    NEED(mask);
+    NEED(n);
+    NEED(nbox);
+    MGIC_CHECK(n[0] >= 0 && n[1] >= 0 && n[2] >= 0, "negative mask extent");
+    MGIC_CHECK(fill_ratio > 0.0, "fill_ratio must be positive");
+    MGIC_CHECK(maxlen >= 1, "maxlen must be >= 1");
+    MGIC_CHECK(cap == 0 || boxes != nullptr, "null argument: boxes");
+    const std::vector<regrid::IBox> v = regrid::cluster(mask, n, fill_ratio, maxlen, nullptr);
+    *nbox = (int)v.size();
+    from_iboxes(v, cap, boxes);
+  });
+}
+MGIC_API int mgic_regrid_levels(int nlev, const int domain0[6], const unsigned char *const *masks,
+                                const int *lat_lo, const int *lat_n, int block_factor,
+                                int max_grid_size, double fill_ratio, int nesting_radius, int cap,
+                                int *nbox, int *boxes, int *new_finest) {
+  return guard([&] {
+    NEED(domain0);
+    NEED(masks);
+    NEED(lat_lo);
+    NEED(lat_n);
+    NEED(nbox);
+    NEED(new_finest);
+    MGIC_CHECK(nlev >= 1, "nlev must be >= 1");
+    MGIC_CHECK(nesting_radius >= 0, "nesting_radius must be >= 0");
+    MGIC_CHECK(cap == 0 || boxes != nullptr, "null argument: boxes");
+    std::vector<regrid::LevelTags> tags((size_t)nlev);
+    for (int l = 0; l < nlev; ++l) {
+      tags[l].mask = masks[l];
+      for (int d = 0; d < 3; ++d) {
+        tags[l].lat_lo[d] = lat_lo[3 * l + d];
+        tags[l].lat_n[d] = lat_n[3 * l + d];
+      }
+    }
+    const regrid::IBox dom = to_iboxes(1, domain0)[0];
+    std::vector<std::vector<regrid::IBox>> out;
+    std::string err;
+    MGIC_CHECK(regrid::regrid_levels(tags, dom, block_factor, max_grid_size, fill_ratio,
+                                     nesting_radius, &out, new_finest, &err) == 0, err);
+    int at = 0;
+    for (int l = 0; l < nlev; ++l) {
+      nbox[l] = (int)out[l].size();
+      if (at < cap) from_iboxes(out[l], cap - at, boxes + 6 * at);
+      at += nbox[l];
+    }
+  });
+}
+MGIC_API int mgic_regrid_owners(int nbox, const int *boxes, int size, int *owners) {
+  return guard([&] {
+    MGIC_CHECK(nbox >= 0 && size >= 1, "bad box count or rank count");
+    if (nbox == 0) return;
+    NEED(boxes);
+    NEED(owners);
+    const std::vector<int> own = regrid::owners(to_iboxes(nbox, boxes), size);
+    for (int i = 0; i < nbox; ++i) owners[i] = own[i];
+  });
 }
 MGIC_API int mgic_field_layout(mgic_field f, int domain[6], int periodic[3], double *dx, int *nbox,
                                int *rank, int *size) {

@@ -1181,6 +1181,115 @@ __global__ __launch_bounds__(256) void k_binary_bh(double *__restrict__ acoef,
              2.0 * M_PI * p.G_Newton * rho_grad * psi_0 - lap;  // SetLevelData.cpp:121-124
 }
 
+// The psi-independent terms of one cell, in the expression order of
+// k_binary_bh (which keeps its own copy, so that its code does not move):
+// rho_grad (GETRHOGRADPHIF of phi_0, SetLevelDataF.ChF:65-103), A2 = A_ij A^ij
+// (SetBinaryBH.H:24-82, SetLevelData.cpp:223-228) and psi_bh (SetBinaryBH.H:85-99)
+struct BhCell {
+  double rho_grad, A2, psi_bh;
+};
+__device__ BhCell bh_cell(const BhParams &p, const int iv[3], double dx) {
+  double loc[3];
+  for (int d = 0; d < 3; ++d) loc[d] = bh_loc(iv[d], dx, p.domlen[d]);
+  BhCell c;
+  c.rho_grad = 0.0;
+  for (int d0 = 0; d0 < 3; ++d0) {
+    double lp[3], lm[3];
+    for (int d = 0; d < 3; ++d) {
+      lp[d] = bh_loc(iv[d] + (d == d0), dx, p.domlen[d]);
+      lm[d] = bh_loc(iv[d] - (d == d0), dx, p.domlen[d]);
+    }
+    const double dphidx = 0.5 / dx * (+bh_phi(p, lp[0], lp[1], lp[2]) - bh_phi(p, lm[0], lm[1], lm[2]));
+    c.rho_grad = c.rho_grad + 0.5 * dphidx * dphidx;
+  }
+  double l1[3] = {loc[0] - p.off1, loc[1], loc[2]}, l2[3] = {loc[0] - p.off2, loc[1], loc[2]};
+  const double r1 = sqrt(l1[0] * l1[0] + l1[1] * l1[1] + l1[2] * l1[2]);
+  const double r2 = sqrt(l2[0] * l2[0] + l2[1] * l2[1] + l2[2] * l2[2]);
+  const double n1[3] = {l1[0] / r1, l1[1] / r1, l1[2] / r1};
+  const double n2[3] = {l2[0] / r2, l2[1] / r2, l2[2] / r2};
+  const double J1[3] = {0.0, 0.0, p.spin1}, J2[3] = {0.0, 0.0, p.spin2};
+  const double P1[3] = {0.0, p.mom1, 0.0}, P2[3] = {0.0, p.mom2, 0.0};
+  const double A11 = bh_Aij(0, 0, r1, r2, n1, n2, J1, J2, P1, P2);
+  const double A22 = bh_Aij(1, 1, r1, r2, n1, n2, J1, J2, P1, P2);
+  const double A33 = bh_Aij(2, 2, r1, r2, n1, n2, J1, J2, P1, P2);
+  const double A12 = bh_Aij(0, 1, r1, r2, n1, n2, J1, J2, P1, P2);
+  const double A13 = bh_Aij(0, 2, r1, r2, n1, n2, J1, J2, P1, P2);
+  const double A23 = bh_Aij(1, 2, r1, r2, n1, n2, J1, J2, P1, P2);
+  c.A2 = pow(A11, 2.0) + pow(A22, 2.0) + pow(A33, 2.0) + 2 * pow(A12, 2.0) + 2 * pow(A13, 2.0) +
+         2 * pow(A23, 2.0);
+  c.psi_bh = p.m1 / r1 + p.m2 / r2;
+  return c;
+}
+
+// set_regrid_condition (SetLevelData.cpp:190-240): the field whose magnitude
+// drives set_grids' tagging.  m is set_m_value(.., K = 0); A2, rho_grad and
+// psi_0 as in k_binary_bh; psi == nullptr: psi = 1 (set_grids evaluates it
+// right after set_initial_conditions).  No ghost cell of psi is read.
+__global__ __launch_bounds__(256) void k_regrid_condition(double *__restrict__ out,
+                                                          const double *__restrict__ psi,
+                                                          const BoxArgs g, double dx,
+                                                          const BhParams p) {
+  const int i = blockIdx.x * TX + threadIdx.x;
+  const int j = blockIdx.y * TY + threadIdx.y;
+  const int k = blockIdx.z;
+  if (i >= g.nx || j >= g.ny) return;
+  const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k};
+  const BhCell c = bh_cell(p, iv, dx);
+  const double rho = 0.5 * 0.0 * 0.0 + 0.0;
+  const double m = (2.0 / 3.0) * (0.0 * 0.0) - 16.0 * M_PI * p.G_Newton * rho;  // K = 0 (:219)
+  const long idx = (long)i + (long)j * g.sy + (long)k * g.sz;
+  const double psi_0 = (psi ? psi[idx] : 1.0) + c.psi_bh;  // :232-233
+  out[idx] = 1.5 * fabs(m) + 1.5 * c.A2 * pow(psi_0, -7.0) +
+             24.0 * M_PI * p.G_Newton * fabs(c.rho_grad) * pow(psi_0, 1.0) + log(psi_0);  // :234-237
+}
+
+// set_tag_cells (SetGrids.cpp:172-207) onto the clustering lattice: a cell of
+// this box is tagged iff |cond| >= tag_val; the tag grown by `grow` cells and
+// clipped to the domain box (no periodic wrap) sets every lattice cell (c^3
+// level cells, lattice index = floor(cell / c)) it reaches in the byte mask
+// over lattice cells [lat_lo, lat_lo + lat_n).  One thread per cell, x
+// fastest; a lane leaves a lattice column to the lane before it when that
+// lane is tagged and reaches the column too (ballot), so a run of tagged
+// cells stores each byte about once per row instead of c times.  Every store
+// writes the same value 1: plain byte stores, any order.
+struct TagArgs {
+  int dom_lo[3], dom_hi[3];
+  int lat_lo[3], lat_n[3];
+  int grow, c;
+};
+__device__ inline int tag_fdiv(int a, int c) { return a >= 0 ? a / c : -((-a + c - 1) / c); }
+__global__ __launch_bounds__(256) void k_tag_lattice(unsigned char *__restrict__ mask,
+                                                     const double *__restrict__ cond,
+                                                     const BoxArgs g, double tag_val,
+                                                     const TagArgs t) {
+  const int i = blockIdx.x * TX + threadIdx.x;
+  const int j = blockIdx.y * TY + threadIdx.y;
+  const int k = blockIdx.z;
+  const bool in = i < g.nx && j < g.ny;
+  bool tagged = false;
+  if (in) tagged = fabs(cond[(long)i + (long)j * g.sy + (long)k * g.sz]) >= tag_val;
+  const unsigned long long wave = __ballot(tagged);  // a wave is one row of 64 cells in x
+  if (!tagged) return;
+  const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k};
+  int la[3], lb[3];
+  for (int d = 0; d < 3; ++d) {
+    const int lo = max(iv[d] - t.grow, t.dom_lo[d]), hi = min(iv[d] + t.grow, t.dom_hi[d]);
+    la[d] = max(tag_fdiv(lo, t.c) - t.lat_lo[d], 0);
+    lb[d] = min(tag_fdiv(hi, t.c) - t.lat_lo[d], t.lat_n[d] - 1);
+  }
+  // columns the previous lane (cell i - 1 of the same row) already stores
+  const int lane = threadIdx.x;
+  if (lane > 0 && ((wave >> (lane - 1)) & 1ull)) {
+    const int phi = min(iv[0] - 1 + t.grow, t.dom_hi[0]);
+    const int pb = min(tag_fdiv(phi, t.c) - t.lat_lo[0], t.lat_n[0] - 1);
+    la[0] = max(la[0], pb + 1);  // (its low end is never above this lane's)
+  }
+  for (int z = la[2]; z <= lb[2]; ++z)
+    for (int y = la[1]; y <= lb[1]; ++y)
+      for (int x = la[0]; x <= lb[0]; ++x)
+        mask[((long)z * t.lat_n[1] + y) * t.lat_n[0] + x] = 1;
+}
+
 // GETLAPLACIANPSIF (SetLevelDataF.ChF:15-58), 2nd-order branch, and
 // GETRHOGRADPHIF (:65-103): undivided-difference loops over `box` with the
 // operand's ghost layer read as is (no BC)
@@ -2275,6 +2384,30 @@ void constant_k_integrand(double *out, const double *psi, const BoxArgs &g, doub
                           const BhParams &p, hipStream_t st) {
   if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
   k_binary_bh<true><<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(out, nullptr, psi, g, dx, p);
+  check_launch();
+}
+
+void regrid_condition(double *out, const double *psi, const BoxArgs &g, double dx,
+                      const BhParams &p, hipStream_t st) {
+  if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
+  k_regrid_condition<<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(out, psi, g, dx, p);
+  check_launch();
+}
+
+void tag_lattice(unsigned char *mask, const double *cond, const BoxArgs &g, double tag_val,
+                 int grow, int c, const int dom_lo[3], const int dom_hi[3], const int lat_lo[3],
+                 const int lat_n[3], hipStream_t st) {
+  if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
+  TagArgs t;
+  for (int d = 0; d < 3; ++d) {
+    t.dom_lo[d] = dom_lo[d];
+    t.dom_hi[d] = dom_hi[d];
+    t.lat_lo[d] = lat_lo[d];
+    t.lat_n[d] = lat_n[d];
+  }
+  t.grow = grow;
+  t.c = c;
+  k_tag_lattice<<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(mask, cond, g, tag_val, t);
   check_launch();
 }
 

@@ -209,6 +209,16 @@ void binary_bh_coefs(double *acoef, double *rhs, const double *psi, const BoxArg
 // set_constant_K_integrand (SetLevelData.cpp:131-180) at psi (nullptr: 1)
 void constant_k_integrand(double *out, const double *psi, const BoxArgs &g, double dx,
                           const BhParams &p, hipStream_t st);
+// set_regrid_condition (SetLevelData.cpp:190-240) at psi (nullptr: 1)
+void regrid_condition(double *out, const double *psi, const BoxArgs &g, double dx,
+                      const BhParams &p, hipStream_t st);
+// set_tag_cells (SetGrids.cpp:172-207) of one box onto a byte mask over lattice
+// cells [lat_lo, lat_lo + lat_n) (lattice index = floor(cell / c), x fastest):
+// cells with |cond| >= tag_val, grown by `grow` and clipped to [dom_lo,
+// dom_hi], set the lattice cells they reach (the mask is cleared by the caller)
+void tag_lattice(unsigned char *mask, const double *cond, const BoxArgs &g, double tag_val,
+                 int grow, int c, const int dom_lo[3], const int dom_hi[3], const int lat_lo[3],
+                 const int lat_n[3], hipStream_t st);
 // GETLAPLACIANPSIF / GETRHOGRADPHIF (SetLevelDataF.ChF), operand ghosts as is
 void lap_psi(double *l, const double *psi, const BoxArgs &g, double dx, hipStream_t st);
 void rho_grad_phi(double *r, const double *phi, const BoxArgs &g, double dx, hipStream_t st);

@@ -24,9 +24,10 @@ NLDivergenceError at the same point, so a diverged solve writes no
 checkpoint.
 
 max_level > 0 (`grid` a list of Grids, coarsest first, finer ones
-Grid(patches=True) properly nested; set_grids' tagging/regridding is out of
-scope, so the hierarchy is given): every step runs per level as the
-reference's loops over ilev do -- coefficients on every level (:154-160),
+Grid(patches=True) properly nested -- what grids.set_grids generates from the
+reference's tagging, or any hierarchy the caller gives): every step runs per
+level as the reference's loops over ilev do -- coefficients on every level
+(:154-160),
 the outer BiCGStab over MultilevelLinearOp with AMR V-cycles as its
 preconditioner (:169-184; AMRSolver), then per level QuadCFInterp of dpsi
 from the coarser level before set_update_psi0 (:189-205), and computeNorm /

@@ -46,6 +46,9 @@ class PoissonParameters:
     max_NL_iterations: int = 4
     max_grid_size: int = 16
     block_factor: int = 8
+    refine_threshold: float = 0.1
+    fill_ratio: float = 0.5
+    buffer_size: int = 3  # read and unused, as in the reference
     verbosity: int = 3
     G_Newton: float = 1.0
     phi_amplitude: float = 0.0
@@ -96,8 +99,11 @@ def read_params(text: str, overrides: Optional[Dict[str, str]] = None) -> Poisso
     p.L = get("L", float)
     p.coarsestDx = p.L / p.N[0]                               # PoissonParameters.cpp:82
     p.domainLength = [p.coarsestDx * n for n in p.N]          # :83-85
-    p.max_grid_size = get("max_grid_size", int)
+    p.refine_threshold = get("refine_threshold", float)      # :88-92
     p.block_factor = get("block_factor", int)
+    p.max_grid_size = get("max_grid_size", int)
+    p.fill_ratio = get("fill_ratio", float)
+    p.buffer_size = get("buffer_size", int)
     if "coefficient_average_type" in kv:                      # :97-108
         s = kv["coefficient_average_type"][0]
         if s == "arithmetic":

@@ -4,7 +4,12 @@ on device: read a params.txt, build the base level, and iterate the
 nonlinear loop.  The per-iteration |dpsi| and linear iteration counts are
 printed as the reference's pout() does.
 
+With --max-level K > 0 the AMR hierarchy is generated first as the reference's
+set_grids does (tagging on the regrid condition, up to K levels above the
+base), and the loop runs over it.
+
 usage: python tools/run_poisson.py [params.txt] [--size N] [--boxes-per-rank x,y,z]
+                                   [--max-level K]
 """
 import argparse
 import json
@@ -22,6 +27,8 @@ def main():
     ap.add_argument("--size", type=int, default=0, help="override N (cells per side)")
     ap.add_argument("--boxes-per-rank", default="1,1,1")
     ap.add_argument("--max-depth", type=int, default=-1)
+    ap.add_argument("--max-level", type=int, default=0,
+                    help="generate up to K AMR levels above the base with set_grids (0: one level)")
     args = ap.parse_args()
     import mg_ic_code_amd as mg
     from mg_ic_code_amd.decomposition import decompose
@@ -32,8 +39,15 @@ def main():
     bpr = tuple(int(v) for v in args.boxes_per_rank.split(","))
     dom, boxes, owners = decompose((n, n, n), 1, boxes_per_rank=bpr)
     grid = mg.Grid(mg.Comm(), dom, boxes, prm.domainLength[0] / n, owners=owners)
+    levels = grid
+    if args.max_level > 0:
+        from mg_ic_code_amd.grids import set_grids
+        levels = set_grids(grid.comm, prm, grid, max_level=args.max_level)
+        for lev, g in enumerate(levels):
+            cells = sum((b[3] - b[0] + 1) * (b[4] - b[1] + 1) * (b[5] - b[2] + 1) for b in g.boxes)
+            print(f"level {lev}: {len(g.boxes)} boxes, {cells} cells")
     t0 = time.perf_counter()
-    res = poisson_solve(grid, prm, max_depth=args.max_depth)
+    res = poisson_solve(levels, prm, max_depth=args.max_depth)
     mg.device_synchronize()
     dt = time.perf_counter() - t0
     for i, (nrm, it) in enumerate(zip(res.dpsi_norms, res.linear_iterations)):
