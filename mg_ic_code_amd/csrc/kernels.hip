@@ -7,7 +7,6 @@
 // wavefronts along x so every wave touches whole 128-byte lines.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <type_traits>
 
 #include "kernels.hpp"
@@ -120,246 +119,35 @@ __global__ __launch_bounds__(256) void k_apply_op(double *__restrict__ lu,
   lu[idx] = lof - ldpsi;                                         // .ChF:229
 }
 
-template <bool BC>
-__global__ __launch_bounds__(256) void k_residual(double *__restrict__ r,
-                                                  const double *__restrict__ u,
-                                                  const double *__restrict__ rhs,
-                                                  const double *__restrict__ a,
-                                                  const double *__restrict__ b, const BoxArgs g,
-                                                  const StencilCoefs s) {
-  const int i = blockIdx.x * TX + threadIdx.x;
-  const int j = blockIdx.y * TY + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i >= g.nx || j >= g.ny) return;
-  const long idx = (long)i + (long)j * g.sy + (long)k * g.sz;
-  const double uc = u[idx];
-  const double res = rhs[idx] - s.alpha * a[idx] * uc;           // .ChF:314-316
-  double ldpsi = lap7(u, idx, uc, i, j, k, g);                   // .ChF:320-329
-  ldpsi = ldpsi * s.dxinv * s.beta * (BC ? s.bval : b[idx]);     // .ChF:331
-  r[idx] = res + ldpsi;                                          // .ChF:333
-}
-
-// z-streaming residual: a thread owns one (i, j) column of a z chunk and
-// carries u(k-1), u(k) in registers; u(k+1) is the only new u load per cell
-// (the x/y neighbours come from L1/L2, loaded as centres by the neighbours).
-// Same expressions as k_residual.
-template <bool BC, class RT>
-__global__ __launch_bounds__(256) void k_residual_z(RT *__restrict__ r,
-                                                    const double *__restrict__ u,
-                                                    const double *__restrict__ rhs,
-                                                    const double *__restrict__ a,
-                                                    const double *__restrict__ b, const BoxArgs g,
-                                                    const StencilCoefs s, int kc) {
-  const int i = blockIdx.x * TX + threadIdx.x;
-  const int j = blockIdx.y * TY + threadIdx.y;
-  const int k0 = blockIdx.z * kc, k1 = min(k0 + kc, g.nz);
-  if (i >= g.nx || j >= g.ny) return;
-  const long col = (long)i + (long)j * g.sy;
-  const bool fx0 = i == 0 && g.bcm[0], fx1 = i == g.nx - 1 && g.bcm[1];
-  const bool fy0 = j == 0 && g.bcm[2], fy1 = j == g.ny - 1 && g.bcm[3];
-  double um = u[col + (long)(k0 - 1) * g.sz];  // ghost plane -1 is allocated
-  double uc = u[col + (long)k0 * g.sz];
-  for (int k = k0; k < k1; ++k) {
-    const long idx = col + (long)k * g.sz;
-    const double up = u[idx + g.sz];  // plane nz (ghost) when k = nz - 1
-    double xm = u[idx - 1], xp = u[idx + 1], ym = u[idx - g.sy], yp = u[idx + g.sy];
-    double zm = um, zp = up;
-    if (fx0) xm = ghost_of(g.bcm[0], g.bcc[0], uc);
-    if (fx1) xp = ghost_of(g.bcm[1], g.bcc[1], uc);
-    if (fy0) ym = ghost_of(g.bcm[2], g.bcc[2], uc);
-    if (fy1) yp = ghost_of(g.bcm[3], g.bcc[3], uc);
-    if (k == 0 && g.bcm[4]) zm = ghost_of(g.bcm[4], g.bcc[4], uc);
-    if (k == g.nz - 1 && g.bcm[5]) zp = ghost_of(g.bcm[5], g.bcc[5], uc);
-    const double res = rhs[idx] - s.alpha * a[idx] * uc;           // .ChF:314-316
-    const double tx = (xp + xm) - 2.0 * uc;
-    const double ty = (yp + ym) - 2.0 * uc;
-    const double tz = (zp + zm) - 2.0 * uc;
-    double ldpsi = (tx + ty) + tz;                                  // .ChF:320-329
-    ldpsi = ldpsi * s.dxinv * s.beta * (BC ? s.bval : b[idx]);     // .ChF:331
-    r[idx] = (RT)(res + ldpsi);  // .ChF:333 (RT = float: the fp64 residual rounded once)
-    um = uc;
-    uc = up;
-  }
-}
-
-// One thread per coarse cell; the 8 fine children are visited in the
-// Fortran k,j,i order so the accumulation res = 0 + t1 + ... + t8
-// (.cpp:177 + .ChF:431-432) rounds exactly like the reference.  The two
-// children of a fine row are one 16-B load per array (fine boxes start on
-// even cells and the valid-lo is 128-B aligned); all loads are issued
-// unconditionally (ghost addresses are always allocated) and the domain BC
-// is folded afterwards, as in lap7.
+// a lane pair as one 16-B (double) / 8-B (float) access
 template <class T>
 __device__ __forceinline__ V2<T> ld2(const T *__restrict__ p) {
   return *reinterpret_cast<const V2<T> *>(p);
 }
 
-// k_residual_z on x-pairs: a thread owns columns (2i, 2i+1) of a z chunk, so
-// u, rhs, a (and b) are one 16-B load per pair and the x neighbours inside
-// the pair come from registers (xl, xr: the cells either side).  Rows are
-// padded and the valid-lo 16-B aligned (FabGeom), so the pair's second cell
-// is always allocated; at an odd nx the last pair writes its first cell
-// only.  Same expressions, per cell, as k_residual.
-// non-temporal forms (NT bit 0: rhs / aCoef / bCoef loads, read once per
-// launch; bit 1: the residual stores): stream them past L2 so u's halo rows,
-// which the neighbouring blocks re-read, stay resident.  Defaults
-// MGIC_RESIDUAL_NT = 3, MGIC_RESTRICT_NT = 1 (512^3 residual 827 -> 789 us,
-// V-cycle +0.9%, A/B over three rounds on one box)
+// non-temporal forms, for the rhs / aCoef / bCoef loads (read once per
+// launch) and the residual stores: stream them past L2 so u's halo rows,
+// which the neighbouring blocks re-read, stay resident.  The residual takes
+// both, the restriction the loads (512^3 residual 827 -> 789 us, V-cycle
+// +0.9%, A/B over three rounds on one box)
 template <class T> struct NTV2;
 template <> struct NTV2<double> { typedef double type __attribute__((ext_vector_type(2))); };
 template <> struct NTV2<float> { typedef float type __attribute__((ext_vector_type(2))); };
-template <bool NT, class T>
+template <class T>
 __device__ __forceinline__ V2<T> ld2n(const T *__restrict__ p) {
-  if constexpr (NT) {
-    const typename NTV2<T>::type v =
-        __builtin_nontemporal_load(reinterpret_cast<const typename NTV2<T>::type *>(p));
-    V2<T> w;
-    w.x = v.x;
-    w.y = v.y;
-    return w;
-  } else {
-    return *reinterpret_cast<const V2<T> *>(p);
-  }
+  const typename NTV2<T>::type v =
+      __builtin_nontemporal_load(reinterpret_cast<const typename NTV2<T>::type *>(p));
+  V2<T> w;
+  w.x = v.x;
+  w.y = v.y;
+  return w;
 }
-template <bool NT, class T>
+template <class T>
 __device__ __forceinline__ void st2n(T *__restrict__ p, const V2<T> &w) {
-  if constexpr (NT) {
-    typename NTV2<T>::type v;
-    v.x = w.x;
-    v.y = w.y;
-    __builtin_nontemporal_store(v, reinterpret_cast<typename NTV2<T>::type *>(p));
-  } else {
-    *reinterpret_cast<V2<T> *>(p) = w;
-  }
-}
-
-// NRM: also the block's max |r| over the cells it writes into
-// partials[linear block id] (AMRMultiGrid's per-iteration max norm, normType
-// 0, taken while r is in registers instead of a second pass over it; a max
-// is exact, so it equals the separate norm bit for bit)
-template <bool BC, class RT, int NT = 0, bool NRM = false>
-__global__ __launch_bounds__(256) void k_residual_z2(RT *__restrict__ r,
-                                                     const double *__restrict__ u,
-                                                     const double *__restrict__ rhs,
-                                                     const double *__restrict__ a,
-                                                     const double *__restrict__ b, const BoxArgs g,
-                                                     const StencilCoefs s, int kc,
-                                                     double *__restrict__ partials = nullptr) {
-  const int i = 2 * (blockIdx.x * TX + threadIdx.x);
-  const int j = blockIdx.y * TY + threadIdx.y;
-  const int k0 = blockIdx.z * kc, k1 = min(k0 + kc, g.nz);
-  double nmax = 0.0;  // the identity of max |x|
-  if (i < g.nx && j < g.ny) {
-    const long col = (long)i + (long)j * g.sy;
-    const bool two = i + 1 < g.nx;
-    const bool fx0 = i == 0 && g.bcm[0];
-    const bool fx1a = i == g.nx - 1 && g.bcm[1], fx1b = i + 1 == g.nx - 1 && g.bcm[1];
-    const bool fy0 = j == 0 && g.bcm[2], fy1 = j == g.ny - 1 && g.bcm[3];
-    double2 um = ld2(u + col + (long)(k0 - 1) * g.sz);  // ghost plane -1 is allocated
-    double2 uc = ld2(u + col + (long)k0 * g.sz);
-    for (int k = k0; k < k1; ++k) {
-      const long idx = col + (long)k * g.sz;
-      const double2 up = ld2(u + idx + g.sz);  // plane nz (ghost) when k = nz - 1
-      const double xl = u[idx - 1], xr = u[idx + 2];
-      const double2 ym = ld2(u + idx - g.sy), yp = ld2(u + idx + g.sy);
-      const double2 rv = ld2n<NT & 1>(rhs + idx), av = ld2n<NT & 1>(a + idx);
-      const double2 bv = BC ? make_double2(s.bval, s.bval) : ld2n<NT & 1>(b + idx);
-      auto cell = [&](double c, double xm, double xp, double ymv, double ypv, double zm, double zp,
-                      double rr, double aa, double bb, bool bxm, bool bxp) {
-        if (bxm) xm = ghost_of(g.bcm[0], g.bcc[0], c);
-        if (bxp) xp = ghost_of(g.bcm[1], g.bcc[1], c);
-        if (fy0) ymv = ghost_of(g.bcm[2], g.bcc[2], c);
-        if (fy1) ypv = ghost_of(g.bcm[3], g.bcc[3], c);
-        if (k == 0 && g.bcm[4]) zm = ghost_of(g.bcm[4], g.bcc[4], c);
-        if (k == g.nz - 1 && g.bcm[5]) zp = ghost_of(g.bcm[5], g.bcc[5], c);
-        const double res = rr - s.alpha * aa * c;            // .ChF:314-316
-        const double tx = (xp + xm) - 2.0 * c;
-        const double ty = (ypv + ymv) - 2.0 * c;
-        const double tz = (zp + zm) - 2.0 * c;
-        double ldpsi = (tx + ty) + tz;                       // .ChF:320-329
-        ldpsi = ldpsi * s.dxinv * s.beta * bb;               // .ChF:331
-        return (RT)(res + ldpsi);                            // .ChF:333
-      };
-      const RT r0 = cell(uc.x, xl, uc.y, ym.x, yp.x, um.x, up.x, rv.x, av.x, bv.x, fx0, fx1a);
-      const RT r1 = cell(uc.y, uc.x, xr, ym.y, yp.y, um.y, up.y, rv.y, av.y, bv.y, false, fx1b);
-      if (two) {
-        V2<RT> w;
-        w.x = r0;
-        w.y = r1;
-        st2n<(NT & 2) != 0>(r + idx, w);
-      } else {
-        r[idx] = r0;
-      }
-      if constexpr (NRM) {
-        nmax = red_op<3>(nmax, fabs((double)r0));
-        if (two) nmax = red_op<3>(nmax, fabs((double)r1));
-      }
-      um = uc;
-      uc = up;
-    }
-  }
-  if constexpr (NRM) {
-    __shared__ double sm[TY];
-    for (int o = 32; o > 0; o >>= 1) nmax = red_op<3>(nmax, __shfl_xor(nmax, o, 64));
-    if (threadIdx.x == 0) sm[threadIdx.y] = nmax;
-    __syncthreads();
-    if (threadIdx.x == 0 && threadIdx.y == 0) {
-      double m = sm[0];
-      for (int w = 1; w < TY; ++w) m = red_op<3>(m, sm[w]);
-      partials[blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)] = m;
-    }
-  }
-}
-
-// one coarse cell of restrictResidual
-template <class T, bool BC, int NT>
-__device__ __forceinline__ void restrict_cell(T *__restrict__ rc, const BoxArgs &cg,
-                                              const T *__restrict__ u, const T *__restrict__ rhs,
-                                              const T *__restrict__ a, const T *__restrict__ b,
-                                              const BoxArgs &fg, const SC<T> &s, int accumulate,
-                                              int ci, int cj, int ck) {
-  const T denom = (T)(2 * 2 * 2);  // .ChF:402
-  const long cidx = (long)ci + (long)cj * cg.sy + (long)ck * cg.sz;
-  T sum = accumulate ? rc[cidx] : (T)0;
-  const int i0 = 2 * ci;
-#pragma unroll
-  for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj) {
-      const int j = 2 * cj + jj, k = 2 * ck + kk;
-      const long row = (long)i0 + (long)j * fg.sy + (long)k * fg.sz;
-      const V2<T> c = ld2(u + row);
-      const V2<T> ym = ld2(u + row - fg.sy), yp = ld2(u + row + fg.sy);
-      const V2<T> zm = ld2(u + row - fg.sz), zp = ld2(u + row + fg.sz);
-      const T xl = u[row - 1], xr = u[row + 2];
-      const V2<T> rv = ld2n<NT & 1>(rhs + row), av = ld2n<NT & 1>(a + row);
-      V2<T> bv;
-      if (BC) bv.x = bv.y = s.bval;
-      else bv = ld2n<NT & 1>(b + row);
-#pragma unroll
-      for (int ii = 0; ii < 2; ++ii) {
-        const int i = i0 + ii;
-        const T uc = ii ? c.y : c.x;
-        T vxm = ii ? c.x : xl, vxp = ii ? xr : c.y;
-        T vym = ii ? ym.y : ym.x, vyp = ii ? yp.y : yp.x;
-        T vzm = ii ? zm.y : zm.x, vzp = ii ? zp.y : zp.x;
-        if (i == 0 && fg.bcm[0]) vxm = ghost_of(fg.bcm[0], (T)fg.bcc[0], uc);
-        if (i == fg.nx - 1 && fg.bcm[1]) vxp = ghost_of(fg.bcm[1], (T)fg.bcc[1], uc);
-        if (j == 0 && fg.bcm[2]) vym = ghost_of(fg.bcm[2], (T)fg.bcc[2], uc);
-        if (j == fg.ny - 1 && fg.bcm[3]) vyp = ghost_of(fg.bcm[3], (T)fg.bcc[3], uc);
-        if (k == 0 && fg.bcm[4]) vzm = ghost_of(fg.bcm[4], (T)fg.bcc[4], uc);
-        if (k == fg.nz - 1 && fg.bcm[5]) vzp = ghost_of(fg.bcm[5], (T)fg.bcc[5], uc);
-        const T tx = (vxp + vxm) - (T)2 * uc;
-        const T ty = (vyp + vym) - (T)2 * uc;
-        const T tz = (vzp + vzm) - (T)2 * uc;
-        T ldpsi = (tx + ty) + tz;                                  // .ChF:416-425
-        T lofdpsi = s.alpha * (ii ? av.y : av.x) * uc;            // .ChF:411-412
-        ldpsi = ldpsi * s.dxinv * s.beta * (ii ? bv.y : bv.x);         // .ChF:427
-        lofdpsi = lofdpsi - ldpsi;                                      // .ChF:429
-        sum = sum + ((ii ? rv.y : rv.x) - lofdpsi) / denom;             // .ChF:431-432
-      }
-    }
-  rc[cidx] = sum;
+  typename NTV2<T>::type v;
+  v.x = w.x;
+  v.y = w.y;
+  __builtin_nontemporal_store(v, reinterpret_cast<typename NTV2<T>::type *>(p));
 }
 
 // XCD-aware tile order for the LDS-staged streaming kernels: consecutive
@@ -378,30 +166,37 @@ __device__ __forceinline__ unsigned xcd_order(unsigned bid, unsigned nb, unsigne
   const unsigned g = bid / G, j = bid - g * G;
   return g * G + (j % 8) * S + j / 8;
 }
-// (x, y, z) tile of this workgroup: lg.w == 0, the 3D grid as launched;
-// else a 1D grid of lg.x * lg.y * lg.z ids in bands of lg.w tiles
+// (x, y, z) tile of this workgroup: a 1D grid of lg.x * lg.y * lg.z ids in
+// bands of lg.w tiles
 __device__ __forceinline__ uint3 tile_of(const uint4 lg) {
-  if (lg.w == 0) return make_uint3(blockIdx.x, blockIdx.y, blockIdx.z);
   const unsigned L = xcd_order(blockIdx.x, gridDim.x, lg.w);
   return make_uint3(L % lg.x, (L / lg.x) % lg.y, L / (lg.x * lg.y));
 }
 
-// k_residual_z2 with the u planes staged in LDS: the workgroup's 128 x 4
-// cells of a plane plus their one-cell halo (6 rows x 132 columns) go to a
-// 4-slot LDS ring, each row loaded once with 16-B loads (the next plane
-// prefetched into registers), one barrier per plane; rhs / aCoef / bCoef
-// and r stream as in k_residual_z2.  Same grid, same cells per thread, same
-// expressions, so the same bits and the same norm partials.
+// VCCOMPUTERES3D, z-streaming on x-pairs: a thread owns columns (2i, 2i+1)
+// of a z chunk, so rhs, a (and b) are one 16-B load per pair and the x
+// neighbours inside the pair come from registers (xl, xr: the cells either
+// side).  Rows are padded and the valid-lo 16-B aligned (FabGeom), so the
+// pair's second cell is always allocated; at an odd nx the last pair writes
+// its first cell only.  The u planes are staged in LDS: the workgroup's
+// 128 x 4 cells of a plane plus their one-cell halo (6 rows x 132 columns)
+// go to a 4-slot LDS ring, each row loaded once with 16-B loads (the next
+// plane prefetched into registers), one barrier per plane; rhs / aCoef /
+// bCoef and r stream past L2 (ld2n, st2n).  Forms measured and not kept: one
+// cell per thread, and x-pairs with u through the L1 (launch_residual below).
+// NRM: also the block's max |r| over the cells it writes into
+// partials[linear tile id] (AMRMultiGrid's per-iteration max norm, normType
+// 0, taken while r is in registers instead of a second pass over it; a max
+// is exact, so it equals the separate norm bit for bit)
 constexpr int kRlCols = 132, kRlRows = 6, kRlPairs = kRlRows * kRlCols / 2;  // 396
-template <bool BC, class RT, int NT = 0, bool NRM = false>
+template <bool BC, class RT, bool NRM>
 __global__ __launch_bounds__(256) void k_residual_zl(RT *__restrict__ r,
                                                      const double *__restrict__ u,
                                                      const double *__restrict__ rhs,
                                                      const double *__restrict__ a,
                                                      const double *__restrict__ b, const BoxArgs g,
                                                      const StencilCoefs s, int kc,
-                                                     double *__restrict__ partials = nullptr,
-                                                     const uint4 lg = uint4{0, 0, 0, 0}) {
+                                                     double *__restrict__ partials, const uint4 lg) {
   __shared__ double Ls[4][kRlRows][kRlCols];
   const uint3 bt = tile_of(lg);
   const int tid = threadIdx.x + TX * threadIdx.y;
@@ -470,8 +265,8 @@ __global__ __launch_bounds__(256) void k_residual_zl(RT *__restrict__ r,
       const double xl = Lk[lr * kRlCols + lc - 1], xr = Lk[lr * kRlCols + lc + 2];
       const double2 ym = *reinterpret_cast<const double2 *>(Lk + (lr - 1) * kRlCols + lc);
       const double2 yp = *reinterpret_cast<const double2 *>(Lk + (lr + 1) * kRlCols + lc);
-      const double2 rv = ld2n<NT & 1>(rhs + idx), av = ld2n<NT & 1>(a + idx);
-      const double2 bv = BC ? make_double2(s.bval, s.bval) : ld2n<NT & 1>(b + idx);
+      const double2 rv = ld2n(rhs + idx), av = ld2n(a + idx);
+      const double2 bv = BC ? make_double2(s.bval, s.bval) : ld2n(b + idx);
       auto cell = [&](double c, double xm, double xp, double ymv, double ypv, double zm, double zp,
                       double rr, double aa, double bb, bool bxm, bool bxp) {
         if (bxm) xm = ghost_of(g.bcm[0], g.bcc[0], c);
@@ -494,7 +289,7 @@ __global__ __launch_bounds__(256) void k_residual_zl(RT *__restrict__ r,
         V2<RT> w;
         w.x = r0;
         w.y = r1;
-        st2n<(NT & 2) != 0>(r + idx, w);
+        st2n(r + idx, w);
       } else {
         r[idx] = r0;
       }
@@ -513,56 +308,45 @@ __global__ __launch_bounds__(256) void k_residual_zl(RT *__restrict__ r,
     if (threadIdx.x == 0 && threadIdx.y == 0) {
       double m = sm[0];
       for (int w = 1; w < TY; ++w) m = red_op<3>(m, sm[w]);
-      const unsigned gx = lg.w ? lg.x : gridDim.x, gy = lg.w ? lg.y : gridDim.y;
-      partials[bt.x + gx * (bt.y + gy * bt.z)] = m;
+      partials[bt.x + lg.x * (bt.y + lg.y * bt.z)] = m;
     }
   }
 }
 
-template <class T, bool BC, int NT = 0>
-__global__ __launch_bounds__(256) void k_restrict(T *__restrict__ rc, const BoxArgs cg,
-                                                  const T *__restrict__ u,
-                                                  const T *__restrict__ rhs,
-                                                  const T *__restrict__ a,
-                                                  const T *__restrict__ b, const BoxArgs fg,
-                                                  const StencilCoefs s64, int accumulate) {
-  const SC<T> s(s64);
-  const int ci = blockIdx.x * TX + threadIdx.x;
-  const int cj = blockIdx.y * TY + threadIdx.y;
-  if (ci >= cg.nx || cj >= cg.ny) return;
-  restrict_cell<T, BC, NT>(rc, cg, u, rhs, a, b, fg, s, accumulate, ci, cj, blockIdx.z);
-}
-
-// The restriction with the fine u planes staged in LDS (the default): a
-// workgroup owns 64 x 4 coarse columns over a chunk of coarse planes; the
+// RESTRICTRESVC3D with the fine u planes staged in LDS.  One thread per
+// coarse cell; the 8 fine children are visited in the Fortran k,j,i order so
+// the accumulation res = 0 + t1 + ... + t8 (.cpp:177 + .ChF:431-432) rounds
+// exactly like the reference.  The two children of a fine row are one 16-B
+// access per array (fine boxes start on even cells and the valid-lo is
+// 128-B aligned); all loads are issued unconditionally (ghost addresses are
+// always allocated) and the domain BC is folded afterwards, as in lap7.
+// A workgroup owns 64 x 4 coarse columns over a chunk of coarse planes; the
 // four fine planes a coarse plane reads (2k-1 .. 2k+2) sit in a 4-slot LDS
 // ring of 10 x 132 doubles (the tile's 8 fine rows and 128 fine columns with
 // their halo), each loaded from global memory once with 16-B loads and the
-// next two prefetched into registers while the current plane is summed.  rhs
-// and aCoef stream from global memory as in k_restrict.  Per coarse cell the
-// expressions and order of restrict_cell, so the same bits.  Loading every
+// next two prefetched into registers while the current plane is summed.  rhs,
+// aCoef and bCoef stream from global memory past L2 (ld2n).  Loading every
 // fine row once into LDS instead of five times per lane through the L1 (c,
-// y -+ 1, z -+ 1) is what pays: k_restrict's L1 sent the L2 twice its
-// compulsory bytes and stalled on pending requests two thirds of the time
-// (profiles/r05q_stream_pmc.txt); short chunks (2 coarse planes) keep the
-// grid large, longer ones re-read fewer halo planes but ran slower.
+// y -+ 1, z -+ 1) is what pays: the plain one-thread-per-coarse-cell kernel's
+// L1 sent the L2 twice its compulsory bytes and stalled on pending requests
+// two thirds of the time (profiles/r05q_stream_pmc.txt); short chunks (2
+// coarse planes) keep the grid large, longer ones re-read fewer halo planes
+// but ran slower.
 constexpr int kRzCols = 132, kRzRows = 10, kRzPairs = kRzRows * kRzCols / 2;  // 660
-template <class T, bool BC, int NT, bool PRE = false>
+template <class T, bool BC, bool PRE>
 __global__ __launch_bounds__(256) void k_restrict_zl(T *__restrict__ rc, const BoxArgs cg,
                                                      const T *__restrict__ u,
                                                      const T *__restrict__ rhs,
                                                      const T *__restrict__ a,
                                                      const T *__restrict__ b, const BoxArgs fg,
                                                      const StencilCoefs s64, int accumulate, int kc,
-                                                     int ntx, int nty, int xcd = 0) {
+                                                     int ntx, int nty, int xcd) {
   __shared__ T Ls[4][kRzRows][kRzCols];
   const SC<T> s(s64);
   const int ntile = ntx * nty;
-  // xcd > 0: bands of xcd tiles in the x-fastest, chunk-slowest order; < 0:
-  // bands of -xcd in the chunk-fastest order (a tile's z chunks together)
-  const int bid = (int)xcd_order(blockIdx.x, gridDim.x, (unsigned)(xcd < 0 ? -xcd : xcd));
-  const int nch = (int)gridDim.x / ntile;
-  const int tile = xcd < 0 ? bid / nch : bid % ntile, chunk = xcd < 0 ? bid % nch : bid / ntile;
+  // bands of xcd tiles in the x-fastest, chunk-slowest order (0: as dispatched)
+  const int bid = (int)xcd_order(blockIdx.x, gridDim.x, (unsigned)xcd);
+  const int tile = bid % ntile, chunk = bid / ntile;
   const int cx0 = (tile % ntx) * TX, cy0 = (tile / ntx) * 4;
   const int k0 = chunk * kc, k1 = min(k0 + kc, cg.nz);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -622,8 +406,8 @@ __global__ __launch_bounds__(256) void k_restrict_zl(T *__restrict__ rc, const B
     for (int q = 0; q < 4; ++q) {
       const int kk = q >> 1, jj = q & 1;
       const long row = (long)(2 * ci) + (long)(2 * cj + jj) * fg.sy + (long)(2 * ck + kk) * fg.sz;
-      rv_[q] = ld2n<NT & 1>(rhs + row);
-      av_[q] = ld2n<NT & 1>(a + row);
+      rv_[q] = ld2n(rhs + row);
+      av_[q] = ld2n(a + row);
     }
   };
   if (PRE && act) cload(k0, crv, cav);
@@ -654,11 +438,11 @@ __global__ __launch_bounds__(256) void k_restrict_zl(T *__restrict__ rc, const B
           const V2<T> zp = *reinterpret_cast<const V2<T> *>(Lp + r * kRzCols + cx);
           const T xl = Lk[r * kRzCols + cx - 1], xr = Lk[r * kRzCols + cx + 2];
           const long row = (long)i0 + (long)j * fg.sy + (long)k * fg.sz;
-          const V2<T> rv = PRE ? crv[kk * 2 + jj] : ld2n<NT & 1>(rhs + row);
-          const V2<T> av = PRE ? cav[kk * 2 + jj] : ld2n<NT & 1>(a + row);
+          const V2<T> rv = PRE ? crv[kk * 2 + jj] : ld2n(rhs + row);
+          const V2<T> av = PRE ? cav[kk * 2 + jj] : ld2n(a + row);
           V2<T> bv;
           if (BC) bv.x = bv.y = s.bval;
-          else bv = ld2n<NT & 1>(b + row);
+          else bv = ld2n(b + row);
 #pragma unroll
           for (int ii = 0; ii < 2; ++ii) {
             const int i = i0 + ii;
@@ -1405,58 +1189,17 @@ inline void check_launch() {
   if (e != hipSuccess) throw Error(kHipErr, std::string("kernel launch: ") + hipGetErrorString(e));
 }
 
-// the LDS-staged residual (MGIC_RESIDUAL_XCD) and restriction
-// (MGIC_RESTRICT_XCD) in XCD bands of S tiles (xcd_order above; 0: the
-// dispatch order; the restriction's S < 0: chunk-fastest bands of -S).
-// The residual takes bands of 16 tiles (4 y rows of the 512^3 plane): its
-// HBM fetch 4.34 -> 3.41 GB per 512^3 launch, 0.782 -> 0.732 ms, 256^3
-// 0.093 -> 0.081 ms, V-cycle +0.3..0.7% (profiles/r05ad_xcd_bands_ab.txt).  The
-// fp64 restriction takes bands of 16 with 4-plane chunks: HBM fetch 3.84 ->
-// 3.41 GB per 512^3 launch (1.19x -> 1.06x the compulsory reads) at the
-// same time (profiles/r05ah_restrict_chunk_band.txt: it is not bound by its
-// HBM bytes); the fp32 one keeps the dispatch order (MGIC_RESTRICT_F_XCD)
-// MGIC_RESTRICT_PRE (mask, 1 fp64 / 2 fp32, default 1): the LDS-staged
-// restriction with constant bCoef loads the next coarse plane's rhs / aCoef
-// rows while it sums the current one; 0 loads them per plane (A/Bs).  fp64:
-// 0.638 -> 0.615 ms at 512^3; fp32 (two coarse planes per workgroup): 1024^3
-// mixed V-cycle 31.05 -> 31.50 ms, so off (profiles/r06zh_restrict_f_pre_ab.txt)
-static int restrict_pre() {
-  static const int v = [] {
-    const char *e = getenv("MGIC_RESTRICT_PRE");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
-static int residual_xcd() {
-  static const int v = [] {
-    const char *e = getenv("MGIC_RESIDUAL_XCD");
-    return e ? atoi(e) : 16;
-  }();
-  return v;
-}
-static int restrict_xcd() {
-  static const int v = [] {
-    const char *e = getenv("MGIC_RESTRICT_XCD");
-    return e ? atoi(e) : 16;
-  }();
-  return v;
-}
-static int restrict_f_xcd() {
-  static const int v = [] {
-    const char *e = getenv("MGIC_RESTRICT_F_XCD");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
-// a 3D tile grid as launched: itself, or 1D with its logical shape in lg
-inline dim3 xcd_grid(const dim3 &g, uint4 &lg) {
-  if (residual_xcd() <= 0) {
-    lg = uint4{0, 0, 0, 0};
-    return g;
-  }
-  lg = uint4{g.x, g.y, g.z, (unsigned)residual_xcd()};
-  return dim3(g.x * g.y * g.z);
-}
+// the LDS-staged residual and restriction in XCD bands of S tiles (xcd_order
+// above; 0: the dispatch order; chunk-fastest bands measured for the
+// restriction and not kept).  The residual takes bands of 16 tiles (4 y rows
+// of the 512^3 plane): its HBM fetch 4.34 -> 3.41 GB per 512^3 launch, 0.782
+// -> 0.732 ms, 256^3 0.093 -> 0.081 ms, V-cycle +0.3..0.7%
+// (profiles/r05ad_xcd_bands_ab.txt).  The fp64 restriction takes bands of 16
+// with 4-plane chunks: HBM fetch 3.84 -> 3.41 GB per 512^3 launch (1.19x ->
+// 1.06x the compulsory reads) at the same time
+// (profiles/r05ah_restrict_chunk_band.txt: it is not bound by its HBM
+// bytes); the fp32 one keeps the dispatch order
+constexpr int kResidualBand = 16, kRestrictBand = 16, kRestrictBandF = 0;
 
 // fp64 -> fp32 over the valid region grown by `grow` (coefficients of the
 // mixed-precision V-cycle); and a float box copy
@@ -1705,15 +1448,16 @@ __device__ __forceinline__ void bicg_stop(BicgState *st, int reason) {
   st->reason = reason;
 }
 
-// The logical block whose rows (and partial) a block takes: its own index, or
-// (BicgState::xr, a grid of whole groups of 8) the XCD-contiguous deal --
-// block b runs on XCD b % 8 and takes logical block (b % 8) (nb / 8) + b / 8,
-// so an XCD streams a contiguous slab of planes (its L2 holds the y / z
-// neighbours of its rows).  The partials stay indexed by logical block, so
-// the sums, and every value, are the same either way.
-__device__ __forceinline__ int bicg_lblock(const BicgState *st) {
+// The logical block whose rows (and partial) a block takes: on a grid of
+// whole groups of 8 the XCD-contiguous deal -- block b runs on XCD b % 8 and
+// takes logical block (b % 8) (nb / 8) + b / 8, so an XCD streams a
+// contiguous slab of planes (its L2 holds the y / z neighbours of its rows)
+// -- else its own index.  The partials stay indexed by logical block, so the
+// sums, and every value, are the same either way (174.3 vs 175.9 us per
+// 128^3 iteration, profiles/r06m_bottom_deal_ab.txt).
+__device__ __forceinline__ int bicg_lblock() {
   const int b = blockIdx.x, nb = gridDim.x;
-  if (!st->xr || (nb & 7)) return b;
+  if (nb & 7) return b;
   return (b & 7) * (nb >> 3) + (b >> 3);
 }
 
@@ -1851,7 +1595,7 @@ __global__ __launch_bounds__(RB) void k_bicgd_apply_dot(BicgState *__restrict__ 
     BicgSten u;
     double rt;
   };
-  const int lb = bicg_lblock(st);
+  const int lb = bicg_lblock();
   bicg_rows(
       g, lb,
       [&](int, int, int, long idx) { return L{bicg_sten_load<BC>(pt, a, b, idx, g), rt[idx]}; },
@@ -1888,7 +1632,7 @@ __global__ __launch_bounds__(RB) void k_bicgd_s(BicgState *__restrict__ st,
   struct L {
     double r, v, lam;
   };
-  const int lb = bicg_lblock(st);
+  const int lb = bicg_lblock();
   bicg_rows(
       g, lb, [&](int, int, int, long idx) { return L{r[idx], v[idx], lam[idx]}; },
       [&](const L &x, int, int, int, long idx, int q) {
@@ -1928,7 +1672,7 @@ __global__ __launch_bounds__(RB) void k_bicgd_apply_dot2(BicgState *__restrict__
     BicgSten u;
     double s;
   };
-  const int lb = bicg_lblock(st);
+  const int lb = bicg_lblock();
   bicg_rows(
       g, lb,
       [&](int, int, int, long idx) { return L{bicg_sten_load<BC>(stv, a, b, idx, g), s[idx]}; },
@@ -1976,7 +1720,7 @@ __global__ __launch_bounds__(RB) void k_bicgd_r(BicgState *__restrict__ st,
     BicgSten u;
     double s, e, pt, rt;
   };
-  const int lb = bicg_lblock(st);
+  const int lb = bicg_lblock();
   bicg_rows(
       g, lb,
       [&](int, int, int, long idx) {
@@ -2056,154 +1800,69 @@ void apply_op(double *lu, const double *u, const double *a, const double *b, con
   check_launch();
 }
 
-// the fp64 residual on LDS-staged u planes (k_residual_zl) in 32-plane
-// chunks: 512^3 0.800 -> 0.775 ms, 256^3 0.100 -> 0.092, V-cycle +0.4%
-// (profiles/r05s_residual_lds_ab.txt); MGIC_RESIDUAL_ZL=0: k_residual_z2
-static bool residual_lds() {
-  static const bool v = [] {
-    const char *e = getenv("MGIC_RESIDUAL_ZL");
-    return !(e && atoi(e) == 0);
-  }();
-  return v;
-}
+// k_residual_zl in z chunks of 16 planes, its tiles in XCD bands
+// (kResidualBand).  fp64 on LDS-staged u planes against u through the L1:
+// 512^3 0.800 -> 0.775 ms, 256^3 0.100 -> 0.092, V-cycle +0.4%
+// (profiles/r05s_residual_lds_ab.txt); 16-plane chunks against 32 with the
+// XCD bands: 0.749 -> 0.737 ms at 512^3, V-cycle +0.6%
+// (profiles/r06zq_residual_chunk_ab.jsonl; the max-norm partials are
+// order-free, so the norm is the same whatever the chunk); fp32 r: 1024^3
+// mixed V-cycle 33.4 -> 32.8 ms (profiles/r05u_residual_f_lds_ab.txt)
+constexpr int kResidualKc = 16;
 
-static int residual_kc_env();
-
-void residual(double *r, const double *u, const double *rhs, const double *a, const double *b,
-              const BoxArgs &g, const StencilCoefs &s, hipStream_t st) {
+template <class RT, bool NRM>
+static void launch_residual(RT *r, const double *u, const double *rhs, const double *a,
+                            const double *b, const BoxArgs &g, const StencilCoefs &s,
+                            double *partials, hipStream_t st) {
   if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
-  const int mode = residual_kc_env();
-  static const int pairs = [] {
-    const char *e = getenv("MGIC_RESIDUAL_PAIRS");
-    return e ? atoi(e) : 1;
-  }();
-  if (mode > 0 && pairs) {  // z-streaming on x-pairs, chunks of `mode` planes
-    const int kc = mode < g.nz ? mode : g.nz;
-    dim3 grid = grid_cells((g.nx + 1) / 2, g.ny, g.nz);
-    grid.z = (unsigned)((g.nz + kc - 1) / kc);
-    static const int nt = [] {
-      const char *e = getenv("MGIC_RESIDUAL_NT");
-      return e ? atoi(e) : 3;
-    }();
-#define MGIC_RZ2(N)                                                                        \
-  do {                                                                                     \
-    if (residual_lds()) {                                                                  \
-      uint4 lg;                                                                            \
-      const dim3 xg = xcd_grid(grid, lg);                                                  \
-      if (s.bconst) k_residual_zl<true, double, N><<<xg, kBlock, 0, st>>>(r, u, rhs, a, b, g, s, kc, nullptr, lg); \
-      else k_residual_zl<false, double, N><<<xg, kBlock, 0, st>>>(r, u, rhs, a, b, g, s, kc, nullptr, lg);         \
-    } else if (s.bconst) k_residual_z2<true, double, N><<<grid, kBlock, 0, st>>>(r, u, rhs, a, b, g, s, kc); \
-    else k_residual_z2<false, double, N><<<grid, kBlock, 0, st>>>(r, u, rhs, a, b, g, s, kc);         \
-  } while (0)
-    switch (nt & 3) {
-      case 1: MGIC_RZ2(1); break;
-      case 2: MGIC_RZ2(2); break;
-      case 3: MGIC_RZ2(3); break;
-      default: MGIC_RZ2(0); break;
-    }
-#undef MGIC_RZ2
-  } else if (mode > 0) {  // z-streaming, chunks of `mode` planes
-    const int kc = mode < g.nz ? mode : g.nz;
-    dim3 grid = grid_cells(g.nx, g.ny, g.nz);
-    grid.z = (unsigned)((g.nz + kc - 1) / kc);
-    if (s.bconst) k_residual_z<true, double><<<grid, kBlock, 0, st>>>(r, u, rhs, a, b, g, s, kc);
-    else k_residual_z<false, double><<<grid, kBlock, 0, st>>>(r, u, rhs, a, b, g, s, kc);
-  } else if (s.bconst) {
-    k_residual<true><<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(r, u, rhs, a, b, g, s);
-  } else {
-    k_residual<false><<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(r, u, rhs, a, b, g, s);
-  }
+  const int kc = kResidualKc < g.nz ? kResidualKc : g.nz;
+  const dim3 t = grid_cells((g.nx + 1) / 2, g.ny, g.nz);
+  const uint4 lg{t.x, t.y, (unsigned)((g.nz + kc - 1) / kc), (unsigned)kResidualBand};
+  const dim3 grid(lg.x * lg.y * lg.z);
+  if (s.bconst) k_residual_zl<true, RT, NRM><<<grid, kBlock, 0, st>>>(r, u, rhs, a, b, g, s, kc, partials, lg);
+  else k_residual_zl<false, RT, NRM><<<grid, kBlock, 0, st>>>(r, u, rhs, a, b, g, s, kc, partials, lg);
   check_launch();
 }
 
-// z chunk of the fp64 residual (MGIC_RESIDUAL_KC): 16 planes for both forms
-// (LDS-staged: 0.749 -> 0.737 ms at 512^3 against 32 with the XCD bands,
-// V-cycle +0.6%, profiles/r06zq_residual_chunk_ab.jsonl; the max-norm
-// partials are order-free, so the norm is the same whatever the chunk)
-static int residual_kc_env() {
-  static const int mode = [] {
-    const char *e = getenv("MGIC_RESIDUAL_KC");
-    return e ? atoi(e) : 16;
-  }();
-  return mode;
+void residual(double *r, const double *u, const double *rhs, const double *a, const double *b,
+              const BoxArgs &g, const StencilCoefs &s, hipStream_t st) {
+  launch_residual<double, false>(r, u, rhs, a, b, g, s, nullptr, st);
 }
 
 long residual_norm_blocks(const BoxArgs &g) {
   if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return 0;
-  const int mode = residual_kc_env();
-  if (mode <= 0) return 0;
-  const int kc = mode < g.nz ? mode : g.nz;
+  const int kc = kResidualKc < g.nz ? kResidualKc : g.nz;
   const dim3 grid = grid_cells((g.nx + 1) / 2, g.ny, g.nz);
   return (long)grid.x * grid.y * ((g.nz + kc - 1) / kc);
 }
 
 void residual_norm(double *r, const double *u, const double *rhs, const double *a, const double *b,
                    const BoxArgs &g, const StencilCoefs &s, double *partials, hipStream_t st) {
-  if (residual_norm_blocks(g) <= 0) throw Error(kBadArg, "residual_norm: streaming residual off");
-  const int mode = residual_kc_env();
-  const int kc = mode < g.nz ? mode : g.nz;
-  dim3 grid = grid_cells((g.nx + 1) / 2, g.ny, g.nz);
-  grid.z = (unsigned)((g.nz + kc - 1) / kc);
-  // the default streams of residual() (MGIC_RESIDUAL_NT = 3: rhs / aCoef
-  // loads and r stores non-temporal)
-  if (residual_lds()) {
-    uint4 lg;
-    const dim3 xg = xcd_grid(grid, lg);
-    if (s.bconst)
-      k_residual_zl<true, double, 3, true><<<xg, kBlock, 0, st>>>(r, u, rhs, a, b, g, s, kc, partials, lg);
-    else
-      k_residual_zl<false, double, 3, true><<<xg, kBlock, 0, st>>>(r, u, rhs, a, b, g, s, kc, partials, lg);
-  } else if (s.bconst)
-    k_residual_z2<true, double, 3, true><<<grid, kBlock, 0, st>>>(r, u, rhs, a, b, g, s, kc, partials);
-  else
-    k_residual_z2<false, double, 3, true><<<grid, kBlock, 0, st>>>(r, u, rhs, a, b, g, s, kc, partials);
-  check_launch();
+  launch_residual<double, true>(r, u, rhs, a, b, g, s, partials, st);
 }
 
 void restrict_residual(double *rc, const BoxArgs &cg, const double *u, const double *rhs,
                        const double *a, const double *b, const BoxArgs &fg, const StencilCoefs &s,
                        hipStream_t st, bool accumulate) {
   if (cg.nx <= 0 || cg.ny <= 0 || cg.nz <= 0) return;
-  static const int nt = [] {
-    const char *e = getenv("MGIC_RESTRICT_NT");
-    return e ? atoi(e) : 1;
-  }();
-  // MGIC_RESTRICT_NT bit 0: non-temporal rhs / aCoef / bCoef loads, for
-  // every bCoef kind (the same switch in restrict_residual_f)
+  MGIC_CHECK(fg.nx == 2 * cg.nx && fg.ny == 2 * cg.ny && fg.nz == 2 * cg.nz,
+             "restrict_residual: fine box must be the coarse box refined by 2");
   const int accu = accumulate ? 1 : 0;
-  // k_restrict_zl, two coarse planes per workgroup (MGIC_RESTRICT_ZL: the
-  // chunk; 0 = k_restrict).  512^3: 0.706 -> 0.641 ms, 256^3 equal, V-cycle
+  // k_restrict_zl against one thread per coarse cell through the L1, two
+  // coarse planes per workgroup: 512^3 0.706 -> 0.641 ms, 256^3 equal, V-cycle
   // +1.4% (chunks 1 .. 32 measured, profiles/r05r_restrict_lds_ab.txt); 4
-  // planes in XCD bands since (restrict_xcd above)
-  static const int zl = [] {
-    const char *e = getenv("MGIC_RESTRICT_ZL");
-    return e ? atoi(e) : 4;
-  }();
-  if (zl > 0 && (nt & 1) && fg.nx == 2 * cg.nx && fg.ny == 2 * cg.ny && fg.nz == 2 * cg.nz) {
-    const int ntx = (cg.nx + TX - 1) / TX, nty = (cg.ny + 3) / 4;
-    const int kc = zl < cg.nz ? zl : cg.nz;
-    const int nb = ntx * nty * ((cg.nz + kc - 1) / kc);
-    if (s.bconst && (restrict_pre() & 1))
-      k_restrict_zl<double, true, 1, true><<<nb, 256, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, accu, kc,
-                                                               ntx, nty, restrict_xcd());
-    else if (s.bconst)
-      k_restrict_zl<double, true, 1><<<nb, 256, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, accu, kc, ntx, nty,
-                                                         restrict_xcd());
-    else
-      k_restrict_zl<double, false, 1><<<nb, 256, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, accu, kc, ntx, nty,
-                                                          restrict_xcd());
-    check_launch();
-    return;
-  }
-  const dim3 grid = grid_cells(cg.nx, cg.ny, cg.nz);
-  if (s.bconst && (nt & 1))
-    k_restrict<double, true, 1><<<grid, kBlock, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, accu);
-  else if (s.bconst)
-    k_restrict<double, true><<<grid, kBlock, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, accu);
-  else if (nt & 1)
-    k_restrict<double, false, 1><<<grid, kBlock, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, accu);
+  // planes in XCD bands since (kRestrictBand above).  Constant bCoef loads
+  // the next coarse plane's rhs / aCoef rows while it sums the current one
+  // (PRE): 0.638 -> 0.615 ms at 512^3
+  const int ntx = (cg.nx + TX - 1) / TX, nty = (cg.ny + 3) / 4;
+  const int kc = 4 < cg.nz ? 4 : cg.nz;
+  const int nb = ntx * nty * ((cg.nz + kc - 1) / kc);
+  if (s.bconst)
+    k_restrict_zl<double, true, true><<<nb, 256, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, accu, kc, ntx,
+                                                          nty, kRestrictBand);
   else
-    k_restrict<double, false><<<grid, kBlock, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, accu);
+    k_restrict_zl<double, false, false><<<nb, 256, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, accu, kc, ntx,
+                                                            nty, kRestrictBand);
   check_launch();
 }
 
@@ -2251,15 +1910,10 @@ void fill_bc(double *u, const BoxArgs &g, hipStream_t st) {
 }
 
 static long reduce_blocks(const BoxArgs &g) {
-  // (MGIC_RED_MAXBLK: a lower cap, for A/Bs; the host loop and the device
-  // loop both size their partials here, so they stay bit-identical)
-  static const long cap = [] {
-    const char *e = getenv("MGIC_RED_MAXBLK");
-    const long v = e ? atol(e) : 0;
-    return v >= 8 && v <= kMaxPartsPerBox ? v : (long)kMaxPartsPerBox;
-  }();
-  long nb = ((long)g.ny * g.nz + RB / 64 - 1) / (RB / 64);  // one wave per row at most
-  return nb > cap ? cap : nb;
+  // (the host loop and the device loop both size their partials here, so
+  // they stay bit-identical)
+  const long nb = ((long)g.ny * g.nz + RB / 64 - 1) / (RB / 64);  // one wave per row at most
+  return nb > kMaxPartsPerBox ? (long)kMaxPartsPerBox : nb;
 }
 
 void blas(int kind, double *x, const double *y, const double *z, double s, double t,
@@ -2352,20 +2006,13 @@ void bicg_p(double *p, const double *v, const double *r, double beta, double c, 
 
 
 // Blocks per item (grid.y = item): sized for the largest item at
-// copy_ept() elements per thread, so the many small items (edges, corners of
+// kCopyEpt elements per thread, so the many small items (edges, corners of
 // a ghost shell) do not each launch the largest item's share of empty blocks
-int copy_ept() {
-  static const int ept = [] {
-    const char *e = getenv("MGIC_COPY_EPT");
-    const int v = e ? atoi(e) : 4;
-    return v > 0 ? v : 1;
-  }();
-  return ept;
-}
+constexpr int kCopyEpt = 4;
 void copy_items(const CopyItem *d_items, int nitems, long max_cells, double *const *src_tab,
                 const double *src_buf, double *const *dst_tab, double *dst_buf, hipStream_t st) {
   if (nitems <= 0 || max_cells <= 0) return;
-  const long per = 256L * copy_ept();
+  const long per = 256L * kCopyEpt;
   long bx = (max_cells + per - 1) / per;
   if (bx > 1024) bx = 1024;
   k_copy_items<double><<<dim3((unsigned)bx, (unsigned)nitems), dim3(256), 0, st>>>(
@@ -2460,83 +2107,29 @@ void incr_grown(double *x, const double *y, const BoxArgs &g, int grow, hipStrea
 // ---- fp32 (mixed-precision V-cycle) variants -------------------------------
 void residual_to_f(float *r, const double *u, const double *rhs, const double *a, const double *b,
                    const BoxArgs &g, const StencilCoefs &s, hipStream_t st) {
-  if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
-  // k_residual_zl<float> in 16-plane chunks by default (MGIC_RESIDUAL_F_ZL;
-  // 0: k_residual_z2): 1024^3 mixed V-cycle 33.4 -> 32.8 ms
-  // (profiles/r05u_residual_f_lds_ab.txt)
-  static const int fzl = [] {
-    const char *e = getenv("MGIC_RESIDUAL_F_ZL");
-    return e ? atoi(e) : 16;
-  }();
-  const int kc0 = fzl > 0 ? fzl : 16;
-  const int kc = kc0 < g.nz ? kc0 : g.nz;
-  dim3 grid = grid_cells((g.nx + 1) / 2, g.ny, g.nz);
-  grid.z = (unsigned)((g.nz + kc - 1) / kc);
-  static const int nt = [] {  // as residual(): MGIC_RESIDUAL_NT, default 3
-    const char *e = getenv("MGIC_RESIDUAL_NT");
-    return e ? atoi(e) : 3;
-  }();
-  // every value of MGIC_RESIDUAL_NT & 3, for both bCoef kinds, as residual()
-#define MGIC_RZ2F(N)                                                                        \
-  do {                                                                                      \
-    if (fzl > 0) {                                                                          \
-      uint4 lg;                                                                             \
-      const dim3 xg = xcd_grid(grid, lg);                                                   \
-      if (s.bconst) k_residual_zl<true, float, N><<<xg, kBlock, 0, st>>>(r, u, rhs, a, b, g, s, kc, nullptr, lg); \
-      else k_residual_zl<false, float, N><<<xg, kBlock, 0, st>>>(r, u, rhs, a, b, g, s, kc, nullptr, lg);         \
-    } else if (s.bconst) k_residual_z2<true, float, N><<<grid, kBlock, 0, st>>>(r, u, rhs, a, b, g, s, kc); \
-    else k_residual_z2<false, float, N><<<grid, kBlock, 0, st>>>(r, u, rhs, a, b, g, s, kc);         \
-  } while (0)
-  switch (nt & 3) {
-    case 1: MGIC_RZ2F(1); break;
-    case 2: MGIC_RZ2F(2); break;
-    case 3: MGIC_RZ2F(3); break;
-    default: MGIC_RZ2F(0); break;
-  }
-#undef MGIC_RZ2F
-  check_launch();
+  launch_residual<float, false>(r, u, rhs, a, b, g, s, nullptr, st);
 }
 
 void restrict_residual_f(float *rc, const BoxArgs &cg, const float *u, const float *rhs,
                          const float *a, const float *b, const BoxArgs &fg, const StencilCoefs &s,
                          hipStream_t st) {
   if (cg.nx <= 0 || cg.ny <= 0 || cg.nz <= 0) return;
-  static const int nt = [] {  // as restrict_residual(): MGIC_RESTRICT_NT, default 1
-    const char *e = getenv("MGIC_RESTRICT_NT");
-    return e ? atoi(e) : 1;
-  }();
-  // k_restrict_zl<float>, two coarse planes per workgroup (MGIC_RESTRICT_F_ZL;
-  // 0: k_restrict): 1024^3 mixed V-cycle 32.6 -> 32.0 ms, FMG 45.4 -> 44.1
-  // (profiles/r05v_restrict_f_lds_ab.txt)
-  static const int fzl = [] {
-    const char *e = getenv("MGIC_RESTRICT_F_ZL");
-    return e ? atoi(e) : 2;
-  }();
-  if (fzl > 0 && (nt & 1) && fg.nx == 2 * cg.nx && fg.ny == 2 * cg.ny && fg.nz == 2 * cg.nz) {
-    const int ntx = (cg.nx + TX - 1) / TX, nty = (cg.ny + 3) / 4;
-    const int kc = fzl < cg.nz ? fzl : cg.nz;
-    const int nb = ntx * nty * ((cg.nz + kc - 1) / kc);
-    if (s.bconst && (restrict_pre() & 2))
-      k_restrict_zl<float, true, 1, true><<<nb, 256, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, 0, kc, ntx,
-                                                              nty, restrict_f_xcd());
-    else if (s.bconst)
-      k_restrict_zl<float, true, 1><<<nb, 256, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, 0, kc, ntx, nty,
-                                                        restrict_f_xcd());
-    else
-      k_restrict_zl<float, false, 1><<<nb, 256, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, 0, kc, ntx, nty,
-                                                         restrict_f_xcd());
-    check_launch();
-    return;
-  }
-  const dim3 grid = grid_cells(cg.nx, cg.ny, cg.nz);
-  if (s.bconst && (nt & 1))
-    k_restrict<float, true, 1><<<grid, kBlock, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, 0);
-  else if (s.bconst)
-    k_restrict<float, true><<<grid, kBlock, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, 0);
-  else if (nt & 1)
-    k_restrict<float, false, 1><<<grid, kBlock, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, 0);
+  MGIC_CHECK(fg.nx == 2 * cg.nx && fg.ny == 2 * cg.ny && fg.nz == 2 * cg.nz,
+             "restrict_residual: fine box must be the coarse box refined by 2");
+  // k_restrict_zl<float>, two coarse planes per workgroup, against one thread
+  // per coarse cell: 1024^3 mixed V-cycle 32.6 -> 32.0 ms, FMG 45.4 -> 44.1
+  // (profiles/r05v_restrict_f_lds_ab.txt); with the next plane's rhs / aCoef
+  // rows prefetched (PRE) 31.05 -> 31.50 ms, so not
+  // (profiles/r06zh_restrict_f_pre_ab.txt)
+  const int ntx = (cg.nx + TX - 1) / TX, nty = (cg.ny + 3) / 4;
+  const int kc = 2 < cg.nz ? 2 : cg.nz;
+  const int nb = ntx * nty * ((cg.nz + kc - 1) / kc);
+  if (s.bconst)
+    k_restrict_zl<float, true, false><<<nb, 256, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, 0, kc, ntx, nty,
+                                                          kRestrictBandF);
   else
-    k_restrict<float, false><<<grid, kBlock, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, 0);
+    k_restrict_zl<float, false, false><<<nb, 256, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, 0, kc, ntx, nty,
+                                                           kRestrictBandF);
   check_launch();
 }
 
@@ -2560,7 +2153,7 @@ void prolong_f(float *uf, const BoxArgs &fg, const float *ec, const BoxArgs &cg,
 void copy_items_f(const CopyItem *d_items, int nitems, long max_cells, float *const *src_tab,
                   const float *src_buf, float *const *dst_tab, float *dst_buf, hipStream_t st) {
   if (nitems <= 0 || max_cells <= 0) return;
-  const long per = 256L * copy_ept();
+  const long per = 256L * kCopyEpt;
   long bx = (max_cells + per - 1) / per;
   if (bx > 1024) bx = 1024;
   k_copy_items<float><<<dim3((unsigned)bx, (unsigned)nitems), dim3(256), 0, st>>>(

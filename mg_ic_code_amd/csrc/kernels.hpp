@@ -69,8 +69,7 @@ void apply_op(double *lu, const double *u, const double *a, const double *b,
 void residual(double *r, const double *u, const double *rhs, const double *a,
               const double *b, const BoxArgs &g, const StencilCoefs &s, hipStream_t st);
 // the same residual plus one max |r| partial per block into partials[0, n)
-// (n = residual_norm_blocks(g); 0 when the streaming residual does not apply:
-// then call residual + reduce_partial instead)
+// (n = residual_norm_blocks(g); 0 for an empty box only)
 long residual_norm_blocks(const BoxArgs &g);
 void residual_norm(double *r, const double *u, const double *rhs, const double *a, const double *b,
                    const BoxArgs &g, const StencilCoefs &s, double *partials, hipStream_t st);
@@ -161,7 +160,6 @@ struct BicgState {
   double rho1, rho2, alpha, beta, omega, nrm, init_norm, rho_next, m, ts, tt;
   double eps, reps, small;
   int it, imax, done, reason, epend, init, restarts, num_restarts, nt;
-  int xr;  // bicg_lblock: the XCD-contiguous row deal (host-set)
 };
 // the reductions' last-block counters (device, zeroed once; each launch
 // leaves its own at zero): this many words

@@ -176,14 +176,7 @@ unsigned long long VariableCoeffPoissonOperator::residualNormQueue(LevelData &lh
                                                                    const LevelData &rhs,
                                                                    bool homogeneous, int normType,
                                                                    double *now) {
-  long total = 0;
-  bool fused = normType == 0;
-  for (int n = 0; fused && n < grid->nlocal(); ++n) {
-    const long nb = kern::residual_norm_blocks(args(n, homogeneous));
-    fused = nb > 0;
-    total += nb;
-  }
-  if (!fused) {
+  if (normType != 0) {
     residualI(lhs, dpsi, rhs, homogeneous);
     *now = normType >= 0 ? norm(lhs, normType) : -1.0;
     return 0;
@@ -195,6 +188,8 @@ unsigned long long VariableCoeffPoissonOperator::residualNormQueue(LevelData &lh
   const hipStream_t st = stream();
   dpsi.exchange(st);  // .cpp:48
   const StencilCoefs s = coefs();
+  long total = 0;
+  for (int n = 0; n < grid->nlocal(); ++n) total += kern::residual_norm_blocks(args(n, homogeneous));
   double *parts = c.d_partials((int)std::max(1L, total));
   long off = 0;
   for (int n = 0; n < grid->nlocal(); ++n) {
@@ -329,22 +324,16 @@ void VariableCoeffPoissonOperator::resetLambda() {
   // the range of lambda over every rank's cells (StencilCoefs::rcp_fast):
   // the denominators the sweeps meet, ghost cells included, are some rank's
   // valid cells
-  static const int allow = [] {
-    const char *e = getenv("MGIC_TB2_RCP");
-    return e ? atoi(e) : 1;
-  }();
-  if (allow) {
-    const double lmax = reduce(4, *m_lambda, nullptr), lmin = -reduce(5, *m_lambda, nullptr);
-    // |lambda| in [2^-e, 2^e], one sign (a <= b, both > 0 in ok)
-    auto within = [&](int e) {
-      const double lo = std::ldexp(1.0, -e), hi = std::ldexp(1.0, e);
-      auto ok = [&](double a, double b) { return a >= lo && b <= hi; };
-      return std::isfinite(lmax) && std::isfinite(lmin) &&
-             ((lmin > 0.0 && ok(lmin, lmax)) || (lmax < 0.0 && ok(-lmax, -lmin)));
-    };
-    rcp_fast_ = within(500);
-    rcp_fast32_ = within(60);
-  }
+  const double lmax = reduce(4, *m_lambda, nullptr), lmin = -reduce(5, *m_lambda, nullptr);
+  // |lambda| in [2^-e, 2^e], one sign (a <= b, both > 0 in ok)
+  auto within = [&](int e) {
+    const double lo = std::ldexp(1.0, -e), hi = std::ldexp(1.0, e);
+    auto ok = [&](double a, double b) { return a >= lo && b <= hi; };
+    return std::isfinite(lmax) && std::isfinite(lmin) &&
+           ((lmin > 0.0 && ok(lmin, lmax)) || (lmax < 0.0 && ok(-lmax, -lmin)));
+  };
+  rcp_fast_ = within(500);
+  rcp_fast32_ = within(60);
 }
 
 void VariableCoeffPoissonOperator::computeLambda() {
@@ -362,15 +351,11 @@ void VariableCoeffPoissonOperator::setTime(double t) {
 // box, no periodic images): every non-domain face is a coarse-fine face, so
 // homogeneousCFInterp before each colour pass (.cpp:296) is a per-face ghost
 // rule of the two cells next to it, which the 3D-block sweep applies in LDS
-// at entry and again between its red and black passes (MGIC_CF_FUSED=0: the
+// at entry and again between its red and black passes (cf_fused_ = 0: the
 // per-colour path).  Mixed faces (part CF, part fine-fine) stay per colour.
 bool VariableCoeffPoissonOperator::cfFusedApplies() {
   if (cf_fused_ >= 0) return cf_fused_ == 1;
-  static const int enabled = [] {
-    const char *e = getenv("MGIC_CF_FUSED");
-    return e ? atoi(e) : 1;
-  }();
-  bool ok = enabled && prm.fused_smoother != 0;
+  bool ok = prm.fused_smoother != 0;
   for (int d = 0; d < 3; ++d) ok = ok && !grid->periodic[d];
   const std::vector<Box> &bx = grid->boxes;
   for (size_t i = 0; ok && i < bx.size(); ++i)
@@ -438,10 +423,7 @@ static constexpr int kDeepDepth = 4, kDeepGrow = 2;
 
 bool VariableCoeffPoissonOperator::deepApplies() const {
   if (!prm.deep_halo || !grid->has_memory_faces() || !grid->tiles_domain()) return false;
-  static const long max_cells = [] {  // deep_halo 2: only levels of boxes up to this size
-    const char *e = getenv("MGIC_DEEP_MAX_CELLS");
-    return e ? atol(e) : 128L * 128 * 128;
-  }();
+  constexpr long max_cells = 128L * 128 * 128;  // deep_halo 2: only levels of boxes up to this size
   // every shell cell must be some box's valid cell within one period
   for (const Box &b : grid->boxes) {
     if (prm.deep_halo == 2 && b.ncells() > max_cells) return false;
@@ -1088,17 +1070,6 @@ BiCGStabSolver::DevWork &BiCGStabSolver::devWork(VariableCoeffPoissonOperator &o
   return *slot;
 }
 
-// the reductions' XCD-contiguous row deal (kern::bicg_lblock; bit-identical
-// either way, 174.3 vs 175.9 us per 128^3 iteration, profiles/
-// r06m_bottom_deal_ab.txt): MGIC_BICG_XCD=0 turns it off
-static int bicg_xcd_deal() {
-  static const int v = [] {
-    const char *e = getenv("MGIC_BICG_XCD");
-    return e ? (atoi(e) != 0 ? 1 : 0) : 1;
-  }();
-  return v;
-}
-
 static int bicg_batch() {
   const char *e = getenv("MGIC_BICG_BATCH");
   const int b = e ? atoi(e) : 4;
@@ -1141,7 +1112,6 @@ int BiCGStabSolver::solveDevice(VariableCoeffPoissonOperator &op, LevelData &phi
   h.num_restarts = prm.numRestarts;
   h.nt = nt;
   h.init = 1;
-  h.xr = bicg_xcd_deal();
   last_init_norm = h.init_norm;
   const BoxArgs &gp = op.boxArgsPlain(0), &gh = op.boxArgs(0, true);
   const StencilCoefs sc = op.stencil();

@@ -37,8 +37,6 @@
 //     keeps neighbouring tiles on one XCD.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "kernels.hpp"
 #include "sweep_util.hpp"
 
@@ -1015,18 +1013,7 @@ static void launch_fused6(T *u_out, T *u_in, const T *rhs, const T *a, const T *
   // the domain BC is applied as the planes enter LDS (no fill launch)
   const int ntx = (g.nx + TX - 1) / TX, nty = (g.ny + TY - 1) / TY;
   static const int slots = resident_slots(k_gsrb_fused6<T, TX, TY, NT, false, false, false>, NT);
-  static const int kc_mode = [] {
-    const char *e = getenv("MGIC_KC_MODE");
-    return e ? atoi(e) : 0;
-  }();
-  int kc = g.nz;
-  if (kc_mode == 1) {  // >= 3072 workgroups
-    while (kc > 16 && (long)ntx * nty * ((g.nz + kc - 1) / kc) < 3072) kc = (kc + 1) / 2;
-  } else if (kc_mode >= 16) {
-    kc = kc_mode < g.nz ? kc_mode : g.nz;
-  } else {
-    kc = choose_kc(ntx * nty, g.nz, slots, 5);
-  }
+  const int kc = choose_kc(ntx * nty, g.nz, slots, 5);
   const int ntz = (g.nz + kc - 1) / kc;
   const int nblocks = ntx * nty * ntz;
   const dim3 grid((unsigned)nblocks), block(NT);
@@ -1047,23 +1034,6 @@ static void launch_fused6(T *u_out, T *u_in, const T *rhs, const T *a, const T *
 #undef MGIC_F6
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) throw Error(kHipErr, std::string("fused sweep launch: ") + hipGetErrorString(e));
-}
-
-static long block_max_cells();
-
-// tile shape, for measurement (MGIC_FUSED_VARIANT): 0 = 128x16 / 512 threads
-// (default: one 106 KB workgroup per CU, 1 KB contiguous rows, u halo 1.29x,
-// coefficient ring 1.16x), 1 = 60x8 / 256 (4 workgroups per CU); a 256x8 /
-// 512 variant measured 0.90 ms, 128x16 / 1024 threads (four waves per SIMD,
-// 107 VGPRs) 0.93 ms, loads two steps ahead (three rotating register sets)
-// 0.89 ms: neither more waves nor deeper prefetch moves it.  512^3 sweep: 0.89 / 1.05 ms; 256^3: 0.142 /
-// 0.168 ms.
-static int fused_variant() {
-  static int v = [] {
-    const char *e = getenv("MGIC_FUSED_VARIANT");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
 }
 
 // the sweep on the tiles covering the region o + [0, e) of the box (the
@@ -1100,47 +1070,33 @@ static void launch_block(T *u_out, T *u_in, const T *rhs, const T *a, const T *b
     throw Error(kHipErr, std::string("block sweep launch: ") + hipGetErrorString(err));
 }
 
-// boxes of at most this many cells take the block kernel (MGIC_BLOCK_MAX_CELLS;
-// 0 = never); MGIC_BLOCK_VARIANT picks its tile for measurement.  100^3: the
+// boxes of at most this many cells take the block kernel.  100^3: the
 // 128^3 bottom of the 512^3 V-cycle runs its sweep pairs through the
 // two-sweep kernel (two launches instead of four; V-cycle +0.1..0.6%, three
 // rounds, round 3), while the 64^3-per-rank bottom of the 8-GPU split and its
 // deep-halo grown boxes (68^3) keep the one-shot block kernel.  (Round 2's
 // 132^3 kept the grown 128^3-per-rank boxes here: 20 us per sweep against 31
 // streamed with single sweeps.)
-static long block_max_cells() {
-  static long v = [] {
-    const char *e = getenv("MGIC_BLOCK_MAX_CELLS");
-    return e ? atol(e) : 100L * 100 * 100;
-  }();
-  return v;
-}
+constexpr long kBlockMaxCells = 100L * 100 * 100;
 
-long gsrb_block_max_cells() { return block_max_cells(); }
-
-static int block_variant() {
-  static int v = [] {
-    const char *e = getenv("MGIC_BLOCK_VARIANT");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
+long gsrb_block_max_cells() { return kBlockMaxCells; }
 
 void gsrb_sweep_fused(double *u_out, double *u_in, const double *rhs, const double *a,
                       const double *b, const BoxArgs &g, const StencilCoefs &s, bool zero_in,
                       double *acc, int kind, hipStream_t st) {
-  if (kind == 3 || (kind != 2 && (long)g.nx * g.ny * g.nz <= block_max_cells())) {
+  if (kind == 3 || (kind != 2 && (long)g.nx * g.ny * g.nz <= kBlockMaxCells)) {
     // 32x8x4 / 256 threads: 64^3 0.0094 ms, 128^3 0.026 ms per sweep; 32x8x8
     // 0.0116 / 0.0278; 16x8x8, 16x8x4, 32x4x4 (128 threads) were slower still
-    if (block_variant() == 1)
-      launch_block<double, 32, 8, 8, 256>(u_out, u_in, rhs, a, b, g, s, zero_in, acc, st);
-    else
-      launch_block<double, 32, 8, 4, 256>(u_out, u_in, rhs, a, b, g, s, zero_in, acc, st);
+    launch_block<double, 32, 8, 4, 256>(u_out, u_in, rhs, a, b, g, s, zero_in, acc, st);
     return;
   }
-  if (fused_variant() == 1)
-    launch_fused6<double, 60, 8, 256>(u_out, u_in, rhs, a, b, g, s, zero_in, acc, st);
-  else if ((g.nx + 131) / 132 < (g.nx + 127) / 128)
+  // streaming tiles: 128x16 / 512 threads (one 106 KB workgroup per CU, 1 KB
+  // contiguous rows, u halo 1.29x, coefficient ring 1.16x): 512^3 sweep 0.89
+  // ms, 256^3 0.142; 60x8 / 256 (4 workgroups per CU) 1.05 / 0.168 ms; 256x8 /
+  // 512 0.90 ms, 128x16 / 1024 threads (four waves per SIMD, 107 VGPRs) 0.93
+  // ms, loads two steps ahead (three rotating register sets) 0.89 ms: neither
+  // more waves nor deeper prefetch moves it
+  if ((g.nx + 131) / 132 < (g.nx + 127) / 128)
     // a box just over a multiple of 128 wide (the deep halo's grown boxes,
     // 256 + 2..4): 132 x 17 tiles (114 KB LDS, same 3 loads / 3 updates per
     // thread) instead of a mostly empty third column of 128-wide tiles
@@ -1155,16 +1111,10 @@ void gsrb_sweep_fused_f(float *u_out, float *u_in, const float *rhs, const float
                         const float *b, const BoxArgs &g, const StencilCoefs &s, bool zero_in,
                         double *acc, int kind, hipStream_t st) {
   // fp32 streaming tiles: 128x32 with 1024 threads (95 KB LDS, four waves
-  // per SIMD): 4.03 ms per 1024^3 sweep against 4.31-4.39 for 128x16 / 512
-  // (MGIC_FUSED_F_VARIANT=1), 128x32 / 512 and 256x16 / 512 (4.45, 4.39)
-  static const int fv = [] {
-    const char *e = getenv("MGIC_FUSED_F_VARIANT");
-    return e ? atoi(e) : 0;
-  }();
-  if (kind == 3 || (kind != 2 && (long)g.nx * g.ny * g.nz <= block_max_cells()))
+  // per SIMD): 4.03 ms per 1024^3 sweep against 4.31-4.39 for 128x16 / 512,
+  // 128x32 / 512 and 256x16 / 512 (4.45, 4.39)
+  if (kind == 3 || (kind != 2 && (long)g.nx * g.ny * g.nz <= kBlockMaxCells))
     launch_block<float, 32, 8, 4, 256>(u_out, u_in, rhs, a, b, g, s, zero_in, acc, st);
-  else if (fv == 1)
-    launch_fused6<float, 128, 16, 512>(u_out, u_in, rhs, a, b, g, s, zero_in, acc, st);
   else
     launch_fused6<float, 128, 32, 1024>(u_out, u_in, rhs, a, b, g, s, zero_in, acc, st);
 }
@@ -1193,12 +1143,8 @@ static void launch_fused_rst(double *u_out, double *u_in, const double *rhs, con
 }
 
 bool gsrb_sweep_fused_restrict_applies(const BoxArgs &g, const BoxArgs &cg, int kind) {
-  static const int enabled = [] {
-    const char *e = getenv("MGIC_FUSED_RESTRICT");
-    return e ? atoi(e) : 1;
-  }();
-  if (!enabled || kind == 0 || kind == 3) return false;
-  if (kind != 2 && (long)g.nx * g.ny * g.nz <= block_max_cells()) return false;  // block kernel
+  if (kind == 0 || kind == 3) return false;
+  if (kind != 2 && (long)g.nx * g.ny * g.nz <= kBlockMaxCells) return false;  // block kernel
   for (int f = 0; f < 6; ++f)
     if (!g.bcm[f]) return false;  // exchanged faces would need a 3-deep shell
   if ((g.nx | g.ny | g.nz) & 1) return false;

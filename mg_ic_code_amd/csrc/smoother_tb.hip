@@ -846,17 +846,12 @@ int tb2_resident_slots() {
 
 // z chunk per workgroup: minimise rounds(kc) * (kc + pipeline fill), the
 // fill being 7 steps rounded up with the chunk to the 2-step unroll.  Chunks
-// go down to 4 planes (MGIC_TB2_KCMIN, for A/Bs): a 128^3 box of 12 tiles
-// then takes 19 chunks of 7 (228 workgroups, one round) instead of 15 of 9
+// go down to 4 planes: a 128^3 box of 12 tiles then takes 19 chunks of 7
+// (228 workgroups, one round) instead of 15 of 9
 int tb2_choose_kc(int tiles, int nz, int slots) {
-  static const int kc_min = [] {
-    const char *e = getenv("MGIC_TB2_KCMIN");
-    const int v = e ? atoi(e) : 4;
-    return v < 1 ? 1 : v;
-  }();
   int best = nz;
   double best_cost = 1e300;
-  for (int kc = nz; kc >= kc_min; --kc) {
+  for (int kc = nz; kc >= 4; --kc) {
     const long nb = (long)tiles * ((nz + kc - 1) / kc);
     const long rounds = (nb + slots - 1) / slots;
     const double cost = (double)rounds * (double)(((kc + 7 + 1) / 2) * 2);
@@ -932,12 +927,8 @@ void launch_tb2(T *u_out, const T *u_in, const T *rhs, const T *a, const BoxArgs
   // ones (the 128^3 bottom) the straddle selects cost more than the lines
   // (MGIC_TB2_TRIM: a mask of launch kinds, for A/Bs; fp64 launches only)
   // the tile order: round-major (sweep::round_tile) when the grid has whole
-  // dispatch rounds (MGIC_TB2_MAP: 0 xcd_tile, 1 round-major)
-  static const int map_env = [] {
-    const char *e = getenv("MGIC_TB2_MAP");
-    return e ? atoi(e) : 1;
-  }();
-  const int rw = map_env == 1 ? tb2_resident_slots<T, TX, TY, NT>() / 8 : 0;
+  // dispatch rounds, else the kernel's xcd_tile
+  const int rw = tb2_resident_slots<T, TX, TY, NT>() / 8;
   static const int trim_mask = [] {
     const char *e = getenv("MGIC_TB2_TRIM");  // bits: 1 ZIN, 2 plain, 4 ACC; 8 any size
     return e ? atoi(e) : 7;

@@ -4,7 +4,7 @@ Test infrastructure only.  `reduce(kind, x, y)` of the operator sums its
 terms in a fully defined order, so the sums can be held to the bit:
 
   * per box, `reduce_blocks` blocks of 256 threads (4 waves): one block per
-    4 rows, at most 2048 (MGIC_RED_MAXBLK unset);
+    4 rows, at most 2048 (kMaxPartsPerBox);
   * rows r = k * ny + j dealt round-robin to the 4 * blocks waves of the box;
   * per lane, four accumulators a0..a3 fed at i, i + 64, i + 128, i + 192
     while i + 192 < nx (i += 256), then a0 alone in steps of 64;

@@ -2,8 +2,8 @@
 """Micro-benchmark of the fine-level smoother: time `relax(nsweeps)` on one
 n^3 box (SetBinaryBH inputs) and print one JSON line with per-sweep time,
 effective GB/s (48 B/cell/pass credited) and a checksum of the result.
-Kernel selection: --kind, MGIC_SWEEPS_PER_LAUNCH (1 or 2), MGIC_FUSED_VARIANT /
-MGIC_FUSED2X_VARIANT / MGIC_BLOCK_VARIANT (tile shapes)."""
+Kernel selection: --kind, MGIC_SWEEPS_PER_LAUNCH (1 or 2), MGIC_TB2_KC (the
+two-sweep launch's z chunk)."""
 import argparse
 import hashlib
 import json

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 R=$(pwd); OUT=$R/gpurun_out/pmc_mem; mkdir -p $OUT
 j=0
-for V in ${VARIANTS:-MGIC_FUSED_VARIANT=0}; do
+for V in ${VARIANTS:-MGIC_SWEEPS_PER_LAUNCH=2}; do
   j=$((j+1)); i=0
   extra=""; [ "$V" = "passes" ] && extra="--no-fused" && V="X=1"
   for C in "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_DRAM_sum" "TCC_EA0_RDREQ_LEVEL_sum TCC_EA0_RDREQ_DRAM_CREDIT_STALL_sum" "TCP_TCC_READ_REQ_LATENCY_sum TCP_TCC_READ_REQ_sum" "GRBM_GUI_ACTIVE TCC_EA0_WRREQ_sum"; do

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Time smoother configurations: each entry of $VARIANTS is a comma-separated
 # list of VAR=value settings, e.g.
-#   VARIANTS="MGIC_SWEEPS_PER_LAUNCH=1 MGIC_SWEEPS_PER_LAUNCH=2,MGIC_FUSED2X_VARIANT=1"
+#   VARIANTS="MGIC_SWEEPS_PER_LAUNCH=1 MGIC_SWEEPS_PER_LAUNCH=2,MGIC_TB2_KC=32"
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
