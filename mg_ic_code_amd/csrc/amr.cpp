@@ -20,14 +20,26 @@ bool coarsenable2(const Box &b) {
 }
 
 // is the box (clipped to the domain in non-periodic directions) covered by
-// the union of the (disjoint) boxes?
+// the union of the (disjoint) boxes and, in periodic directions, of their
+// periodic images?  (The part of r past a periodic face is what k_cf_interp
+// reads through the wrap: it has to be there.)
 bool covered_by(Box r, const Grid &g) {
-  for (int d = 0; d < 3; ++d) {  // (periodic images: the in-domain part is checked)
+  int len[3];
+  for (int d = 0; d < 3; ++d) {
+    len[d] = g.domain.size(d);
+    if (g.periodic[d]) continue;
     r.lo[d] = std::max(r.lo[d], g.domain.lo[d]);
     r.hi[d] = std::min(r.hi[d], g.domain.hi[d]);
   }
   long v = 0;
-  for (const Box &b : g.boxes) v += r.intersect(b).ncells();
+  for (const Box &b : g.boxes)
+    for (int sz = -1; sz <= 1; ++sz)
+      for (int sy = -1; sy <= 1; ++sy)
+        for (int sx = -1; sx <= 1; ++sx) {
+          if ((sx && !g.periodic[0]) || (sy && !g.periodic[1]) || (sz && !g.periodic[2])) continue;
+          const int sh[3] = {sx * len[0], sy * len[1], sz * len[2]};
+          v += r.intersect(b.shifted(sh)).ncells();  // images of disjoint boxes are disjoint
+        }
   return v == r.ncells();
 }
 

@@ -1,8 +1,10 @@
 """numpy restatement of the AMR multi-level operators -- TEST INFRASTRUCTURE ONLY.
 
-The checker for mg_ic_code_amd/csrc/amr.cpp on
-hierarchies with one box per level.  fp64, every expression in the GPU
-kernels' order, so results are bit-identical:
+The checker for mg_ic_code_amd/csrc/amr.cpp: AMROracle
+with one box per level, MultiBoxAMROracle with a list of disjoint boxes per
+level (unions that are not boxes, sibling exchange, periodic directions).
+fp64, every expression in the GPU kernels' order, so results are
+bit-identical:
 
 * coarse-fine interpolation ([Chombo] QuadCFInterp, restated; the
   reference calls homogeneousCFInterp at
@@ -21,6 +23,8 @@ Parity unpinned against Chombo (its AMR code is not in the reference tree).
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 import oracle
@@ -29,8 +33,10 @@ W0, W1, W2 = 8.0 / 15.0, 2.0 / 3.0, -0.2
 
 
 class Level:
-    def __init__(self, box, dx, a, b, domain, bc_lo, bc_hi, bc_value, alpha, beta):
+    def __init__(self, box, dx, a, b, domain, bc_lo, bc_hi, bc_value, alpha, beta,
+                 periodic=(0, 0, 0)):
         self.box = tuple(box)  # lo0 lo1 lo2 hi0 hi1 hi2
+        self.periodic = tuple(periodic)
         self.dx = dx
         self.a, self.b = np.asarray(a, np.float64), np.asarray(b, np.float64)
         self.domain = tuple(domain)
@@ -51,6 +57,8 @@ class Level:
         return out
 
     def domain_face(self, dir, side):
+        if self.periodic[dir]:  # a face on a periodic boundary is an exchanged face
+            return False
         b, d = self.box, self.domain
         return b[3 + dir] == d[3 + dir] if side else b[dir] == d[dir]
 
@@ -76,9 +84,11 @@ class Level:
                     c = (1.0 if side else -1.0) * self.dx * self.bc_value
                     u[tuple(g)] = near + c
 
-    def cf_interp(self, u, coarse=None, cov=(), cdomain=None):
+    def cf_interp(self, u, coarse=None, cov=(), cdomain=None, phistar=None):
         """ghosts of the non-domain faces from the coarse level (lv, full
-        array) or zero; cov: coarsened fine boxes (covered test)"""
+        array) or zero; cov: coarsened fine boxes (covered test).  phistar
+        (loc, dir, d0, d1) -> phi*: the coarse level given some other way
+        (MultiBoxAMROracle: several coarse boxes, periodic wrap)"""
         b = self.box
         for dir in range(3):
             ax = 2 - dir
@@ -98,7 +108,9 @@ class Level:
                 i2 = list(gi)
                 i2[ax] = i2[ax] + 2 * step
                 f1, f2 = u[tuple(i1)], u[tuple(i2)]
-                if coarse is None:
+                if phistar is not None:
+                    ps = phistar(loc, dir, d0, d1)
+                elif coarse is None:
                     ps = np.zeros(A0.shape)
                 else:
                     ps = self._phistar(loc, dir, d0, d1, coarse, cov, cdomain)
@@ -125,6 +137,15 @@ class Level:
                 ok &= ~inside
             return ok
 
+        def at_clipped(p):  # (an unusable neighbour may lie outside the array)
+            return at([np.clip(p[k], cb[k] - 1, cb[3 + k] + 1) for k in range(3)])
+
+        return self._phistar_core(gf, gc, d0, d1, at_clipped, usable)
+
+    @staticmethod
+    def _phistar_core(gf, gc, d0, d1, at, usable):
+        """phi* from the coarse values at(p) and the usable(p) test (p: three
+        index arrays, coarse index space), in k_cf_interp's order"""
         c0 = at(gc)
         d1v, d2v, xt = [], [], []
         for d in (d0, d1):
@@ -134,8 +155,8 @@ class Level:
             pm = list(gc)
             pm[d] = gc[d] - 1
             okp, okm = usable(pp), usable(pm)
-            vp = np.where(okp, at([np.clip(pp[k], cb[k] - 1, cb[3 + k] + 1) for k in range(3)]), 0.0)
-            vm = np.where(okm, at([np.clip(pm[k], cb[k] - 1, cb[3 + k] + 1) for k in range(3)]), 0.0)
+            vp = np.where(okp, at(pp), 0.0)
+            vm = np.where(okm, at(pm), 0.0)
             both = okp & okm
             g1 = np.where(both, (vp - vm) * 0.5, np.where(okp, vp - c0, np.where(okm, c0 - vm, 0.0)))
             g2 = np.where(both, (vp - 2.0 * c0) + vm, 0.0)
@@ -149,7 +170,7 @@ class Level:
                 p[d1] = gc[d1] + s1
                 ok = usable(p)
                 allok &= ok
-                v.append(np.where(ok, at([np.clip(p[k], cb[k] - 1, cb[3 + k] + 1) for k in range(3)]), 0.0))
+                v.append(np.where(ok, at(p), 0.0))
         d12 = np.where(allok, (((v[3] - v[2]) - v[1]) + v[0]) * 0.25, 0.0)
         ps = c0
         for t in range(2):
@@ -458,3 +479,338 @@ class AMROracle:
         incr(phis, E, 1.0)
         R = self.residual_ml(phis, rhss, False)
         return it, self.norm(R, norm_type)
+
+
+# ---------------------------------------------------------------- multi-box
+def _isect(a, b):
+    lo = [max(a[d], b[d]) for d in range(3)]
+    hi = [min(a[3 + d], b[3 + d]) for d in range(3)]
+    return None if any(l > h for l, h in zip(lo, hi)) else tuple(lo + hi)
+
+
+def _sl(region, box, ghost):
+    """slices of a region (global indices) in the (z, y, x) array of a box
+    with `ghost` ghost layers"""
+    return tuple(slice(region[d] - box[d] + ghost, region[3 + d] - box[d] + ghost + 1)
+                 for d in (2, 1, 0))
+
+
+def coarsen_box(b):
+    return tuple([v // 2 for v in b[:3]] + [(v + 1) // 2 - 1 for v in b[3:]])
+
+
+def _valid(x):
+    return x[1:-1, 1:-1, 1:-1]
+
+
+class MultiBoxAMROracle(AMROracle):
+    """AMROracle with a list of disjoint boxes per level (amr.cpp on any
+    properly nested hierarchy: unions that are not boxes, faces that are part
+    fine-fine and part coarse-fine, covered tangential neighbours, periodic
+    directions).
+
+    levels: list of dict(boxes=[box, ...], a=[array per box], b=[array per
+    box]) from coarsest; level 0 is one box, the domain.  A multi-level
+    vector is a FLAT list of per-box arrays, level by level, boxes in the
+    order given (self.ix[l]: the flat indices of level l; split() regroups);
+    with one box per level that is AMROracle's list, and its methods keep
+    their conventions (full arrays with ghost 1, except where AMROracle takes
+    valid ones).  Every box has its own ghosts: a cell outside the level can
+    be the ghost of two boxes with two different values.
+
+    Ghost fill of a level, in the order of amr.cpp / op.cpp: the coarse-fine
+    interpolation on every non-domain face of every box (whole faces), the
+    sibling exchange valid -> 1-deep face ghosts (through periodic images),
+    the physical BC.  dot_fsum: dot products and 1-/2-norms summed with
+    math.fsum over all cells of a level (default: per box, then over boxes)
+    -- the two bracket what any summation order can give."""
+
+    def __init__(self, levels, dx0, domain0, alpha=1.0, beta=-1.0, bc_lo=(0, 0, 0),
+                 bc_hi=(0, 0, 0), bc_value=0.0, n_pre=4, n_post=4, base=None,
+                 periodic=(0, 0, 0), dot_fsum=False):
+        self.periodic = tuple(int(p) for p in periodic)
+        self.dot_fsum = dot_fsum
+        self.B, self.dom, self.ix = [], [], []
+        dom, dx, n = tuple(domain0), dx0, 0
+        for lv in levels:
+            boxes = [tuple(b) for b in lv["boxes"]]
+            self.B.append([Level(bx, dx, a, b, dom, bc_lo, bc_hi, bc_value, alpha, beta,
+                                 self.periodic) for bx, a, b in zip(boxes, lv["a"], lv["b"])])
+            self.dom.append(dom)
+            self.ix.append(list(range(n, n + len(boxes))))
+            n += len(boxes)
+            dom = tuple(2 * v if i < 3 else 2 * v + 1 for i, v in enumerate(dom))
+            dx = dx / 2
+        assert len(self.B[0]) == 1 and self.B[0][0].box == tuple(domain0), "level 0: the domain"
+        self.L = [bs[0] for bs in self.B]  # (dx per level; level 0's box)
+        self.n_pre, self.n_post = n_pre, n_post
+        base = dict(base or {})
+        self.o = oracle.OracleMG([self.L[0].box], self.L[0].box, dx0, alpha=alpha, beta=beta,
+                                 periodic=self.periodic, bc_lo=bc_lo, bc_hi=bc_hi,
+                                 bc_value=bc_value, **base)
+        self.o.set(0, oracle.ACOEF, 0, self.L[0].a)
+        self.o.set(0, oracle.BCOEF, 0, self.L[0].b)
+        self.o.setup()
+        self._plans()
+
+    def _plans(self):
+        self.xplan, self.dplan, self.cmask = [], [None], [None]
+        for l, bs in enumerate(self.B):
+            dom = self.dom[l]
+            ln = [dom[3 + d] - dom[d] + 1 for d in range(3)]
+            sh = [(-1, 0, 1) if self.periodic[d] else (0,) for d in range(3)]
+            plan = []
+            for i, bi in enumerate(bs):
+                for dir in range(3):
+                    for side in (0, 1):
+                        r = list(bi.box)  # the cells adjacent to the face
+                        r[dir] = r[3 + dir] = bi.box[3 + dir] + 1 if side else bi.box[dir] - 1
+                        for j, bj in enumerate(bs):
+                            for sz in sh[2]:
+                                for sy in sh[1]:
+                                    for sx in sh[0]:
+                                        s = (sx * ln[0], sy * ln[1], sz * ln[2])
+                                        x = _isect(r, tuple(v + s[k % 3]
+                                                            for k, v in enumerate(bj.box)))
+                                        if x is None:
+                                            continue
+                                        src = tuple(v - s[k % 3] for k, v in enumerate(x))
+                                        plan.append((i, _sl(x, bi.box, 1), j, _sl(src, bj.box, 1)))
+            self.xplan.append(plan)
+            if l == 0:
+                continue
+            cdom = self.dom[l - 1]
+            mask = np.zeros(tuple(cdom[3 + d] - cdom[d] + 1 for d in (2, 1, 0)), bool)
+            down = []
+            for i, bi in enumerate(bs):
+                c = coarsen_box(bi.box)
+                assert all(v % 2 == 0 for v in bi.box[:3]) and all(v % 2 for v in bi.box[3:]), \
+                    "fine boxes must be coarsenable by 2"
+                mask[_sl(c, cdom, 0)] = True
+                for j, bj in enumerate(self.B[l - 1]):
+                    x = _isect(c, bj.box)
+                    if x is not None:
+                        down.append((i, _sl(x, c, 0), j, _sl(x, bj.box, 0)))
+            self.cmask.append(mask)
+            self.dplan.append(down)
+
+    # ------------------------------------------------------------ vectors
+    def split(self, xs):
+        return [[xs[i] for i in ix] for ix in self.ix]
+
+    def lv(self, xs, l):
+        return [xs[i] for i in self.ix[l]]
+
+    def cov(self, l):
+        return [coarsen_box(b.box) for b in self.B[l]]
+
+    def zeros_ml(self):
+        return [b.full() for bs in self.B for b in bs]
+
+    def full_ml(self, arrs):
+        return [b.full(a) for b, a in zip([b for bs in self.B for b in bs], arrs)]
+
+    def glob(self, l, us):
+        """the level's valid data in one array over its domain (NaN where
+        the level has no cell)"""
+        dom = self.dom[l]
+        g = np.full(tuple(dom[3 + d] - dom[d] + 1 for d in (2, 1, 0)), np.nan)
+        for b, u in zip(self.B[l], us):
+            g[_sl(b.box, dom, 0)] = _valid(u)
+        return g
+
+    # -------------------------------------------------------------- ghosts
+    def _phistar(self, l, b, cg, loc, dir, d0, d1):
+        cdom, mask, per = self.dom[l - 1], self.cmask[l], self.periodic
+        gf = [loc[d] + b.box[d] for d in range(3)]
+        gc = [np.floor_divide(g, 2) for g in gf]
+
+        def wrap(p):  # cf_usable's test and wrap; indices into the domain arrays
+            ok, q = np.ones(p[0].shape, bool), []
+            for d in range(3):
+                n = cdom[3 + d] - cdom[d] + 1
+                if per[d]:
+                    q.append(np.mod(p[d] - cdom[d], n))
+                else:
+                    ok &= (p[d] >= cdom[d]) & (p[d] <= cdom[3 + d])
+                    q.append(np.clip(p[d] - cdom[d], 0, n - 1))
+            return ok, (q[2], q[1], q[0])
+
+        def at(p):
+            return cg[wrap(p)[1]]
+
+        def usable(p):
+            ok, q = wrap(p)
+            return ok & ~mask[q]
+
+        return Level._phistar_core(gf, gc, d0, d1, at, usable)
+
+    def cf_interp(self, l, us, coarse_us=None):
+        """CF ghosts of every non-domain face of every box of level l (whole
+        faces: the part a sibling box covers is the exchange's to replace)"""
+        if coarse_us is None:
+            for b, u in zip(self.B[l], us):
+                for dir in range(3):
+                    for side in (0, 1):
+                        if b.domain_face(dir, side):
+                            continue
+                        g, n1, n2 = ([slice(1, -1)] * 3 for _ in range(3))
+                        g[2 - dir], n1[2 - dir], n2[2 - dir] = (-1, -2, -3) if side else (0, 1, 2)
+                        u[tuple(g)] = (W0 * 0.0 + W1 * u[tuple(n1)]) + W2 * u[tuple(n2)]
+            return
+        cg = self.glob(l - 1, coarse_us)
+        for b, u in zip(self.B[l], us):
+            b.cf_interp(u, phistar=lambda loc, dir, d0, d1, b=b: self._phistar(l, b, cg, loc, dir,
+                                                                               d0, d1))
+
+    def exchange(self, l, us):
+        for i, di, j, sj in self.xplan[l]:
+            us[i][di] = us[j][sj]
+
+    def fill(self, l, us, coarse_us, hom_phys):
+        """CF ghosts (coarse_us None: homogeneous), exchange, physical BC"""
+        if l > 0:
+            self.cf_interp(l, us, coarse_us)
+        self.exchange(l, us)
+        for b, u in zip(self.B[l], us):
+            b.fill_bc(u, hom_phys)
+
+    def relax(self, l, es, rs, n):
+        for _ in range(n):
+            for colour in (0, 1):
+                self.fill(l, es, None, True)
+                for b, e, r in zip(self.B[l], es, rs):
+                    b.gsrb_pass(e, r, colour)
+
+    def amr_residual(self, l, phis, phis_coarse, rhss, hom=False):
+        self.fill(l, phis, phis_coarse, hom)
+        return [b.residual(p, r) for b, p, r in zip(self.B[l], phis, rhss)]
+
+    def put_covered(self, l, coarse_valid, fine_avg=None):
+        """the averaged fine data (None: zero) onto the covered cells of the
+        coarse level's valid arrays"""
+        for i, si, j, sj in self.dplan[l]:
+            coarse_valid[j][sj] = 0.0 if fine_avg is None else fine_avg[i][si]
+
+    def prolong_const(self, l, es, ecs):
+        cg, cdom = self.glob(l - 1, ecs), self.dom[l - 1]
+        for b, e in zip(self.B[l], es):
+            c = cg[_sl(coarsen_box(b.box), cdom, 0)]
+            f = _valid(e)
+            for kk in range(2):
+                for jj in range(2):
+                    for ii in range(2):
+                        f[kk::2, jj::2, ii::2] = f[kk::2, jj::2, ii::2] + c
+
+    # ---------------------------------------------------------------- driver
+    def init_residual(self, phis, rhss):
+        """phis: full arrays (modified: ghosts), rhss: valid arrays; returns
+        the residuals (valid arrays)"""
+        self.phis, self.rhss = phis, rhss
+        res = []
+        for l in range(len(self.B)):
+            res += self.amr_residual(l, self.lv(phis, l), self.lv(phis, l - 1) if l else None,
+                                     self.lv(rhss, l))
+        for l in range(1, len(self.B)):
+            self.put_covered(l, self.lv(res, l - 1))
+        self.res = res
+        return res
+
+    def cycle(self, l):
+        if l == 0:
+            AMROracle.cycle(self, 0)
+            return
+        I, Ic = self.ix[l], self.ix[l - 1]
+        es = [b.full() for b in self.B[l]]
+        rs = self.lv(self.res, l)
+        self.relax(l, es, rs, self.n_pre)
+        for i, e in zip(I, es):
+            self.corr[i] = e
+        r = self.amr_residual(l, es, None, rs, True)  # AMRRestrict
+        self.put_covered(l, self.lv(self.res, l - 1), [average_down(x) for x in r])
+        self.cycle(l - 1)
+        ecs = [self.corr[i] for i in Ic]
+        self.prolong_const(l, es, ecs)
+        for i, x in zip(I, self.amr_residual(l, es, ecs, rs, True)):  # AMRUpdateResidual
+            self.res[i] = x
+        des = [b.full() for b in self.B[l]]
+        self.relax(l, des, self.lv(self.res, l), self.n_post)
+        for e, de in zip(es, des):
+            _valid(e)[...] = _valid(e) + _valid(de)
+
+    def _accumulate(self, xs):
+        """xs += corr, then the covered cells from the finer level's average"""
+        for x, c in zip(xs, self.corr):
+            _valid(x)[...] = _valid(x) + _valid(c)
+        for l in range(len(self.B) - 1, 0, -1):
+            self.put_covered(l, [_valid(x) for x in self.lv(xs, l - 1)],
+                             [average_down(_valid(x)) for x in self.lv(xs, l)])
+
+    def iteration(self):
+        self.corr = [None] * len(self.phis)
+        self.cycle(len(self.B) - 1)
+        self._accumulate(self.phis)
+        return self.init_residual(self.phis, self.rhss)
+
+    # ------------------------------------------- MultilevelLinearOp + BiCGStab
+    def zero_covered(self, xs):
+        for l in range(1, len(self.B)):
+            self.put_covered(l, [_valid(x) for x in self.lv(xs, l - 1)])
+
+    def apply_op(self, xs, hom=True):
+        out = []
+        for l, bs in enumerate(self.B):
+            us = self.lv(xs, l)
+            self.fill(l, us, self.lv(xs, l - 1) if l else None, hom)
+            out += [b.full(-b.residual(u, np.zeros(b.shape))) for b, u in zip(bs, us)]
+        self.zero_covered(out)
+        return out
+
+    def residual_ml(self, phis, rhss, hom=False):
+        out = []
+        for l, bs in enumerate(self.B):
+            r = self.amr_residual(l, self.lv(phis, l), self.lv(phis, l - 1) if l else None,
+                                  [_valid(x) for x in self.lv(rhss, l)], hom)
+            out += [b.full(x) for b, x in zip(bs, r)]
+        self.zero_covered(out)
+        return out
+
+    def _sum(self, l, arrs):
+        if self.dot_fsum:
+            return math.fsum(v for a in arrs for v in a.ravel())
+        s = 0.0
+        for a in arrs:
+            s += float(np.sum(a))
+        return s
+
+    def dot(self, xs, ys):
+        return sum(self.weight(l) * self._sum(l, [_valid(x) * _valid(y) for x, y in
+                                                  zip(self.lv(xs, l), self.lv(ys, l))])
+                   for l in range(len(self.B)))
+
+    def norm(self, xs, ord=0):
+        if ord == 0:
+            return max(float(np.abs(_valid(x)).max()) for x in xs)
+        f = np.abs if ord == 1 else np.square
+        s = sum(self.weight(l) * self._sum(l, [f(_valid(x)) for x in self.lv(xs, l)])
+                for l in range(len(self.B)))
+        return s if ord == 1 else float(np.sqrt(s))
+
+    def precondition(self, rs, iters):
+        n = len(self.B)
+        es = self.zeros_ml()
+        for i in range(iters):
+            if i == 0:
+                self.res = [_valid(r).copy() for r in rs]
+            else:
+                self.res = []
+                for l in range(n):
+                    self.res += self.amr_residual(l, self.lv(es, l),
+                                                  self.lv(es, l - 1) if l else None,
+                                                  [_valid(x) for x in self.lv(rs, l)], True)
+                for l in range(1, n):
+                    self.put_covered(l, self.lv(self.res, l - 1))
+            self.corr = [None] * len(es)
+            self.cycle(n - 1)
+            self._accumulate(es)
+        return es

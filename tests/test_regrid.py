@@ -172,12 +172,17 @@ def _three_level_tags():
     return c, [((0, 0, 0), m0), (lo1, m1), (lo2, m2)]
 
 
-def _nested(fine, coarse, dom_fine, radius):
-    """coarsen(fine, 2) grown by radius (clipped to the coarse domain) lies in
-    the union of `coarse` boxes, for every fine box."""
+def _nested(fine, coarse, dom_fine, radius, periodic=False):
+    """coarsen(fine, 2) grown by radius (clipped to the coarse domain; periodic:
+    wrapped round it) lies in the union of `coarse` boxes, for every fine box."""
     dom_c = tuple(v // 2 for v in dom_fine)
     n = dom_c[3] - dom_c[0] + 1
     cover = R.paint([tuple(v - dom_c[i % 3] for i, v in enumerate(b)) for b in coarse], (n, n, n))
+    for f in fine if periodic else ():
+        ix = [[(v - dom_c[d]) % n for v in range(f[d] // 2 - radius, f[3 + d] // 2 + radius + 1)]
+              for d in range(3)]
+        if not np.all(cover[np.ix_(ix[2], ix[1], ix[0])] == 1):
+            return False
     for f in fine:
         lo = [max(f[d] // 2 - radius, dom_c[d]) - dom_c[d] for d in range(3)]
         hi = [min(f[3 + d] // 2 + radius, dom_c[3 + d]) - dom_c[d] for d in range(3)]
@@ -285,8 +290,14 @@ def comm():
     return mg.Comm()
 
 
-def _centred_params(bh1_offset="0.0"):
+TWO_HOLES = "two holes"  # params.txt's own configuration (both punctures)
+
+
+def _centred_params(bh1_offset="0.0", **more):
     from mg_ic_code_amd.params import read_params_file
+    if bh1_offset == TWO_HOLES:
+        return read_params_file(PARAMS, overrides=dict(
+            block_factor="8", max_grid_size="16", fill_ratio="0.5", **more))
     return read_params_file(PARAMS, overrides=dict(
         bh1_offset=bh1_offset, bh2_bare_mass="0.0", bh2_spin="0.0", bh2_momentum="0.0",
         block_factor="8", max_grid_size="16", fill_ratio="0.5"))
@@ -455,16 +466,17 @@ N0 = 32
 _REF = {}
 
 
-def _reference_hierarchy():
-    """The restatement's set_grids for the centred configuration (computed
-    once): per pass the level conditions, tagVal margins, lattice fills and
-    boxes."""
-    if _REF:
-        return _REF
-    prm = _centred_params()
+def _reference_hierarchy(bh1_offset="0.0", n0=N0, **more):
+    """The restatement's set_grids for the one-hole configuration (the
+    centred one by default) or TWO_HOLES, computed once each: per pass the
+    level conditions, tagVal margins, lattice fills and boxes."""
+    key = (bh1_offset, n0) + tuple(sorted(more.items()))
+    if key in _REF:
+        return _REF[key]
+    prm = _centred_params(bh1_offset, **more)
     bh = prm.bh()
     c, _ = R.lattice_params(prm.block_factor, prm.max_grid_size)
-    dom0 = (0, 0, 0, N0 - 1, N0 - 1, N0 - 1)
+    dom0 = (0, 0, 0, n0 - 1, n0 - 1, n0 - 1)
     levels = [[dom0]]
     top, margins, fills = 0, {}, {}
     more = True
@@ -472,7 +484,7 @@ def _reference_hierarchy():
         more = False
         old_top = top
         tags = []
-        dom, dx = dom0, prm.L / N0
+        dom, dx = dom0, prm.L / n0
         for l, boxes in enumerate(levels):
             conds = [R.regrid_condition(bh, b[:3], b[3:], dx) for b in boxes]
             mx = max(np.abs(a).max() for a in conds)
@@ -490,8 +502,8 @@ def _reference_hierarchy():
         levels = [[dom0]] + new[:top]
         if top < 2 and top > old_top:
             more = True
-    _REF.update(prm=prm, levels=levels, margins=margins, fills=fills)
-    return _REF
+    _REF[key] = dict(prm=prm, levels=levels, margins=margins, fills=fills)
+    return _REF[key]
 
 
 def _union_box(boxes):
@@ -517,12 +529,12 @@ def test_reference_hierarchy_of_the_centred_configuration():
     assert abs(ref["fills"][0] - 0.85) < 0.01 and abs(ref["fills"][1] - 0.96) < 0.01
 
 
-def _device_hierarchy(comm, bh1_offset="0.0"):
+def _device_hierarchy(comm, bh1_offset="0.0", n0=N0, **more):
     import mg_ic_code_amd as mg
     G = _grids()
-    prm = _centred_params(bh1_offset)
-    dom0 = (0, 0, 0, N0 - 1, N0 - 1, N0 - 1)
-    base = mg.Grid(comm, dom0, [dom0], prm.L / N0)
+    prm = _centred_params(bh1_offset, **more)
+    dom0 = (0, 0, 0, n0 - 1, n0 - 1, n0 - 1)
+    base = mg.Grid(comm, dom0, [dom0], prm.L / n0)
     return prm, G.set_grids(comm, prm, base, max_level=2)
 
 
@@ -578,6 +590,77 @@ def test_nl_solve_on_generated_hierarchy_matches_oracle(comm):
         err = np.linalg.norm(got - c) / np.linalg.norm(c)
         print("level", l, "relative L2 difference", err)
         assert np.linalg.norm(got - c) <= 1e-10 * np.linalg.norm(c), l
+
+
+# ---- a generated hierarchy whose union is not a box.  The off-centre hole
+# and params.txt's two equal holes give cubes of 16^3 boxes on every level
+# (at a 16^3 and a 32^3 base, for thresholds 0.1 ... 0.7), so: two unequal
+# holes, the light one further out, on a 16^3 base.  Level 1 is the whole
+# 32^3 index space as 8 boxes; level 2 is a 16 x 32 x 32 slab of four boxes
+# around the heavy hole with a bar of two boxes (16 and 8 cells long) towards
+# the light one on its x-lo face: a T, with faces that are part fine-fine and
+# part coarse-fine and concave corners.
+NONBOX = dict(refine_threshold="0.3", bh2_bare_mass="0.1", bh2_offset="-20.0")
+NONBOX_N0 = 16
+
+
+def _is_box(boxes):
+    u = tuple(min(b[d] for b in boxes) for d in range(3)) + \
+        tuple(max(b[3 + d] for b in boxes) for d in range(3))
+    return sum(R.box_cells(b) for b in boxes) == R.box_cells(u)
+
+
+def test_reference_hierarchy_whose_union_is_not_a_box():
+    for bh1_offset, kw in ((OFF_CENTRE, {}), (TWO_HOLES, {})):  # (why neither is used)
+        assert all(_is_box(bs) for bs in _reference_hierarchy(bh1_offset, NONBOX_N0, **kw)["levels"])
+    ref = _reference_hierarchy(TWO_HOLES, NONBOX_N0, **NONBOX)
+    print("margins", ref["margins"], "fills", ref["fills"])
+    assert all(m > 1e-9 for m in ref["margins"].values())  # no cell on the tagging threshold
+    lv = ref["levels"]
+    assert [len(bs) for bs in lv] == [1, 8, 6]
+    assert all(R.disjoint(bs) for bs in lv)
+    assert _is_box(lv[1]) and not _is_box(lv[2])
+    assert _nested(lv[2], lv[1], (0, 0, 0, 63, 63, 63), 2)
+
+
+def test_regrid_is_not_periodic_aware():
+    # DESIGN.md 3f, the limitation that stands: tags and nesting are clipped to
+    # the domain, so a hole near a face gives a level 2 on that face with no
+    # level 1 at the opposite one -- properly nested on a bounded domain, not
+    # on a periodic one, where AMRSolver rejects it (test_amr_multibox.py)
+    lv = _reference_hierarchy("30.0")["levels"]
+    assert max(b[3] for b in lv[2]) == 4 * N0 - 1 and min(b[0] for b in lv[1]) > 0
+    assert _nested(lv[2], lv[1], (0, 0, 0, 4 * N0 - 1, 4 * N0 - 1, 4 * N0 - 1), 1)
+    assert not _nested(lv[2], lv[1], (0, 0, 0, 4 * N0 - 1, 4 * N0 - 1, 4 * N0 - 1), 1, periodic=True)
+
+
+@pytest.mark.gpu
+def test_nl_solve_on_generated_non_box_hierarchy_matches_oracle(comm):
+    # poisson_solve on set_grids' output (16^3 + 8 x 16^3 + 6 boxes in a T)
+    # against the oracle loop on the same box lists, every box with its own
+    # ghosts; the comparisons of test_nl_solve_on_generated_hierarchy_matches_oracle
+    from mg_ic_code_amd.nl import poisson_solve
+    from tests.nl_ref import oracle_poisson_solve_amr
+    ref = _reference_hierarchy(TWO_HOLES, NONBOX_N0, **NONBOX)
+    assert all(m > 1e-9 for m in ref["margins"].values()), ref["margins"]
+    prm, grids = _device_hierarchy(comm, TWO_HOLES, NONBOX_N0, **NONBOX)
+    assert [g.boxes for g in grids] == ref["levels"]
+    assert not _is_box(grids[2].boxes)
+    res = poisson_solve(grids, prm, max_depth=2, max_NL_iterations=2)
+    psi_o, norms_o, iters_o = oracle_poisson_solve_amr(
+        prm, [grids[0].boxes[0]] + [g.boxes for g in grids[1:]], NONBOX_N0, max_depth=2, n_nl=2)
+    print("linear iterations", res.linear_iterations, iters_o, "norms", res.dpsi_norms, norms_o)
+    assert res.linear_iterations[:2] == iters_o[:2]
+    np.testing.assert_allclose(res.dpsi_norms[:2], norms_o[:2], rtol=1e-6)
+    for l, g in enumerate(grids):
+        got = [None] * len(g.boxes)
+        for k in range(g.num_local):
+            got[g.boxes.index(g.local_box(k))] = res.psi[l].download(k)
+        want = [p[1:-1, 1:-1, 1:-1] for p in psi_o[l]]
+        num = np.sqrt(sum(np.sum((a - b) ** 2) for a, b in zip(got, want)))
+        den = np.sqrt(sum(np.sum(b ** 2) for b in want))
+        print("level", l, "relative L2 difference", num / den)
+        assert num <= 1e-10 * den, l
 
 
 def _free_port():
