@@ -453,6 +453,34 @@ MGIC_API int mgic_field_grchombo_vars(mgic_field psi, int n, int k0, int nk, con
                                       double *out, int out_on_device);
 MGIC_API int mgic_field_solver_vars(mgic_field dpsi, mgic_field rhs, mgic_field psi, int n, int k0,
                                     int nk, const double bh[13], double *out, int out_on_device);
+/* ---- phi_0 as a stored field (the c_phi_0 component set_initial_conditions
+ * fills, SetLevelData.cpp:32-71).  phi holds the scalar-field profile at the
+ * centre of every cell of each local box and of the one ghost layer next to
+ * each face: loc = (iv + 0.5) dx - L/2, also for ghost cells outside the
+ * domain or under a coarse-fine boundary.  It is never exchanged, BC-filled
+ * or interpolated.  The *_phi entry points are the ones of the same name
+ * above with phi_0 read from phi instead of evaluated as the Gaussian; phi
+ * must have the layout of the other fields (MGIC_EBADARG otherwise).  Filled
+ * with MGIC_PHI_GAUSSIAN they give the analytic entry points' values bit for
+ * bit.  A caller's own profile is uploaded with mgic_field_upload(phi, n,
+ * host, 1). */
+#define MGIC_PHI_GAUSSIAN 0 /* amplitude exp(-r^2 / wavelength)  (MyPhiFunction.H:14-15) */
+#define MGIC_PHI_SINE 1     /* amplitude sum_d sin(2 pi x_d wavelength / L)  (:18-20) */
+/* fill phi (valid cells and the ghost shell of depth one) with a built-in
+ * profile; bh[13] as mgic_field_binary_bh (domain_length, phi_amplitude and
+ * phi_wavelength are read).  An unknown profile is MGIC_EBADARG. */
+MGIC_API int mgic_field_fill_phi(mgic_field phi, int profile, const double bh[13]);
+MGIC_API int mgic_field_nl_coefs_phi(mgic_field psi, mgic_field phi, mgic_field acoef,
+                                     mgic_field rhs, const double bh[13]);
+MGIC_API int mgic_field_nl_integrand_phi(mgic_field psi, mgic_field phi, mgic_field out,
+                                         const double bh[13]);
+MGIC_API int mgic_field_regrid_condition_phi(mgic_field psi, mgic_field phi, mgic_field out,
+                                             const double bh[13]);
+MGIC_API int mgic_field_grchombo_vars_phi(mgic_field psi, mgic_field phi, int n, int k0, int nk,
+                                          const double bh[13], double *out, int out_on_device);
+MGIC_API int mgic_field_solver_vars_phi(mgic_field dpsi, mgic_field rhs, mgic_field psi,
+                                        mgic_field phi, int n, int k0, int nk, const double bh[13],
+                                        double *out, int out_on_device);
 /* the field's layout: domain, periodicity, dx, number of boxes (all ranks),
  * this rank and the job size; box i's extent, owner rank and local index
  * (-1 if not local); a barrier over the field's communicator */

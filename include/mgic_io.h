@@ -53,6 +53,19 @@ MGIC_IO_API int mgic_io_write_solver_data(const char *filename, int nlevels,
                                           const mgic_field *psi, const double bh[13],
                                           const int *ref_ratio, int iter);
 
+/* The two writers with phi_0 stored (mgic.h, "phi_0 as a stored field"):
+ * phi[l] is level l's phi_0 field, on psi[l]'s layout.  The "phi" component of
+ * the final data and the "phi_0" component of the solver data are copied from
+ * it; every other component is as above. */
+MGIC_IO_API int mgic_io_write_final_data_phi(const char *filename, int nlevels,
+                                             const mgic_field *psi, const mgic_field *phi,
+                                             const double bh[13], int max_level,
+                                             const int *ref_ratio);
+MGIC_IO_API int mgic_io_write_solver_data_phi(const char *filename, int nlevels,
+                                              const mgic_field *dpsi, const mgic_field *rhs,
+                                              const mgic_field *psi, const mgic_field *phi,
+                                              const double bh[13], const int *ref_ratio, int iter);
+
 /* The same two layouts from host arrays (tests, and callers whose data is
  * already on the host).  kind 0: final data (31 components), 1: solver data
  * (10).  Level l has nbox[l] boxes (6 ints each, all levels concatenated in

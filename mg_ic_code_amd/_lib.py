@@ -219,6 +219,12 @@ SIGNATURES = {
     "mgic_amr_solve": [H, POINTER(H), POINTER(H), POINTER(SolveParams), PI, PD],
     "mgic_field_grchombo_vars": [H, c_int, c_int, c_int, PD, c_void_p, c_int],
     "mgic_field_solver_vars": [H, H, H, c_int, c_int, c_int, PD, c_void_p, c_int],
+    "mgic_field_fill_phi": [H, c_int, PD],
+    "mgic_field_nl_coefs_phi": [H, H, H, H, PD],
+    "mgic_field_nl_integrand_phi": [H, H, H, PD],
+    "mgic_field_regrid_condition_phi": [H, H, H, PD],
+    "mgic_field_grchombo_vars_phi": [H, H, c_int, c_int, c_int, PD, c_void_p, c_int],
+    "mgic_field_solver_vars_phi": [H, H, H, H, c_int, c_int, c_int, PD, c_void_p, c_int],
     "mgic_field_layout": [H, PI, PI, PD, PI, PI, PI],
     "mgic_field_box": [H, c_int, PI, PI, PI],
     "mgic_field_barrier": [H],
@@ -322,6 +328,8 @@ IO_SIGNATURES = {
     "mgic_io_last_error": [],
     "mgic_io_write_final_data": [c_char_p, c_int, PH, PD, c_int, PI],
     "mgic_io_write_solver_data": [c_char_p, c_int, PH, PH, PH, PD, PI, c_int],
+    "mgic_io_write_final_data_phi": [c_char_p, c_int, PH, PH, PD, c_int, PI],
+    "mgic_io_write_solver_data_phi": [c_char_p, c_int, PH, PH, PH, PH, PD, PI, c_int],
     "mgic_io_write_host": [c_char_p, c_int, c_int, PI, PI, PI, PD, PI, PD, c_int, c_int],
 }
 _io = None

@@ -664,8 +664,10 @@ static void *scratch_device(size_t bytes) {
   }
   return b.p;
 }
+// phi: the stored phi_0 (the *_phi entry points), or null: evaluated in place
 static void output_vars_capi(int kind, mgic_field psi, mgic_field dpsi, mgic_field rhs, int n,
-                             int k0, int nk, const double bh[13], double *out, int on_device) {
+                             int k0, int nk, const double bh[13], double *out, int on_device,
+                             mgic_field phi = nullptr) {
   NEED(psi);
   NEED(bh);
   NEED(out);
@@ -677,6 +679,7 @@ static void output_vars_capi(int kind, mgic_field psi, mgic_field dpsi, mgic_fie
     check_same_layout(g, *dpsi->f, "dpsi");
     check_same_layout(g, *rhs->f, "rhs");
   }
+  if (phi) check_same_layout(g, *phi->f, "phi");
   MGIC_CHECK(n >= 0 && n < g.nlocal(), "bad local box index");
   const FabGeom &fg = g.geom[n];
   MGIC_CHECK(k0 >= 0 && nk >= 1 && k0 + nk <= fg.nz, "plane range outside the box");
@@ -687,8 +690,11 @@ static void output_vars_capi(int kind, mgic_field psi, mgic_field dpsi, mgic_fie
   const kern::BhParams p = bh_params(bh);
   double *d = out;
   if (!on_device) d = static_cast<double *>(scratch_device(bytes));
-  kern::output_vars(kind, d, u.p[n], kind ? dpsi->f->p[n] : nullptr, kind ? rhs->f->p[n] : nullptr,
-                    a, k0, nk, g.dx, p, st);
+  const double *dp = kind ? dpsi->f->p[n] : nullptr, *rp = kind ? rhs->f->p[n] : nullptr;
+  if (phi)
+    kern::output_vars_phi(kind, d, u.p[n], dp, rp, phi->f->p[n], a, k0, nk, g.dx, p, st);
+  else
+    kern::output_vars(kind, d, u.p[n], dp, rp, a, k0, nk, g.dx, p, st);
   if (!on_device) {
     MGIC_HIP(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, st));
     MGIC_HIP(hipStreamSynchronize(st));
@@ -714,6 +720,83 @@ MGIC_API int mgic_field_regrid_condition(mgic_field psi, mgic_field out, const d
     for (int n = 0; n < g.nlocal(); ++n)
       kern::regrid_condition(out->f->p[n], psi ? psi->f->p[n] : nullptr, g.box_args_plain(n), g.dx,
                              p, g.comm->stream());
+  });
+}
+// ---- phi_0 as a stored field (SetLevelData.cpp:32-71's c_phi_0): filled once
+// from a built-in profile (or uploaded by the caller), then read by the
+// *_phi generators in place of the analytic Gaussian
+MGIC_API int mgic_field_fill_phi(mgic_field phi, int profile, const double bh[13]) {
+  return guard([&] {
+    NEED(phi);
+    NEED(bh);
+    MGIC_CHECK(profile == kern::kPhiGaussian || profile == kern::kPhiSine,
+               "unknown phi profile " + std::to_string(profile));
+    const Grid &g = *phi->f->grid;
+    const kern::BhParams p = bh_params(bh);
+    for (int n = 0; n < g.nlocal(); ++n)
+      kern::fill_phi(profile, phi->f->p[n], g.box_args_plain(n), g.dx, p, g.comm->stream());
+  });
+}
+MGIC_API int mgic_field_nl_coefs_phi(mgic_field psi, mgic_field phi, mgic_field acoef,
+                                     mgic_field rhs, const double bh[13]) {
+  return guard([&] {
+    NEED(phi);
+    NEED(acoef);
+    NEED(rhs);
+    NEED(bh);
+    const Grid &g = *acoef->f->grid;
+    if (psi) check_same_layout(g, *psi->f, "psi");
+    check_same_layout(g, *phi->f, "phi");
+    check_same_layout(g, *rhs->f, "rhs");
+    const kern::BhParams p = bh_params(bh);
+    for (int n = 0; n < g.nlocal(); ++n)
+      kern::binary_bh_coefs_phi(acoef->f->p[n], rhs->f->p[n], psi ? psi->f->p[n] : nullptr,
+                                phi->f->p[n], g.box_args_plain(n), g.dx, p, g.comm->stream());
+  });
+}
+MGIC_API int mgic_field_nl_integrand_phi(mgic_field psi, mgic_field phi, mgic_field out,
+                                         const double bh[13]) {
+  return guard([&] {
+    NEED(phi);
+    NEED(out);
+    NEED(bh);
+    const Grid &g = *out->f->grid;
+    if (psi) check_same_layout(g, *psi->f, "psi");
+    check_same_layout(g, *phi->f, "phi");
+    const kern::BhParams p = bh_params(bh);
+    for (int n = 0; n < g.nlocal(); ++n)
+      kern::constant_k_integrand_phi(out->f->p[n], psi ? psi->f->p[n] : nullptr, phi->f->p[n],
+                                     g.box_args_plain(n), g.dx, p, g.comm->stream());
+  });
+}
+MGIC_API int mgic_field_regrid_condition_phi(mgic_field psi, mgic_field phi, mgic_field out,
+                                             const double bh[13]) {
+  return guard([&] {
+    NEED(phi);
+    NEED(out);
+    NEED(bh);
+    const Grid &g = *out->f->grid;
+    if (psi) check_same_layout(g, *psi->f, "psi");
+    check_same_layout(g, *phi->f, "phi");
+    const kern::BhParams p = bh_params(bh);
+    for (int n = 0; n < g.nlocal(); ++n)
+      kern::regrid_condition_phi(out->f->p[n], psi ? psi->f->p[n] : nullptr, phi->f->p[n],
+                                 g.box_args_plain(n), g.dx, p, g.comm->stream());
+  });
+}
+MGIC_API int mgic_field_grchombo_vars_phi(mgic_field psi, mgic_field phi, int n, int k0, int nk,
+                                          const double bh[13], double *out, int out_on_device) {
+  return guard([&] {
+    NEED(phi);
+    output_vars_capi(0, psi, nullptr, nullptr, n, k0, nk, bh, out, out_on_device, phi);
+  });
+}
+MGIC_API int mgic_field_solver_vars_phi(mgic_field dpsi, mgic_field rhs, mgic_field psi,
+                                        mgic_field phi, int n, int k0, int nk, const double bh[13],
+                                        double *out, int out_on_device) {
+  return guard([&] {
+    NEED(phi);
+    output_vars_capi(1, psi, dpsi, rhs, n, k0, nk, bh, out, out_on_device, phi);
   });
 }
 MGIC_API int mgic_field_norm(mgic_field x, int ord, double *out) {

@@ -370,9 +370,14 @@ extern "C" {
 
 MGIC_IO_API const char *mgic_io_last_error(void) { return g_err.c_str(); }
 
-MGIC_IO_API int mgic_io_write_final_data(const char *filename, int nlevels, const mgic_field *psi,
-                                         const double bh[13], int max_level,
-                                         const int *ref_ratio) {
+}  // extern "C"
+
+namespace {
+
+// phi: null (phi_0 evaluated in place), or one stored phi_0 field per level
+int write_final_data(const char *filename, int nlevels, const mgic_field *psi,
+                     const mgic_field *phi, const double bh[13], int max_level,
+                     const int *ref_ratio) {
   return guard([&] {
     need(psi, "psi");
     need(bh, "bh");
@@ -385,17 +390,20 @@ MGIC_IO_API int mgic_io_write_final_data(const char *filename, int nlevels, cons
     J.ref_ratio.assign(ref_ratio, ref_ratio + nlevels);
     std::vector<mgic_field> lead(psi, psi + nlevels);
     for (auto f : lead) need(f, "psi[l]");
+    for (int l = 0; phi && l < nlevels; ++l) need(phi[l], "phi[l]");
     write_fields(filename ? filename : "vcPoissonFinal.3d.hdf5", J, lead,
                  [&](int l, int n, int k0, int nk, double *out) {
-                   mg(mgic_field_grchombo_vars(psi[l], n, k0, nk, bh, out, 0));
+                   if (phi)
+                     mg(mgic_field_grchombo_vars_phi(psi[l], phi[l], n, k0, nk, bh, out, 0));
+                   else
+                     mg(mgic_field_grchombo_vars(psi[l], n, k0, nk, bh, out, 0));
                  });
   });
 }
 
-MGIC_IO_API int mgic_io_write_solver_data(const char *filename, int nlevels,
-                                          const mgic_field *dpsi, const mgic_field *rhs,
-                                          const mgic_field *psi, const double bh[13],
-                                          const int *ref_ratio, int iter) {
+int write_solver_data(const char *filename, int nlevels, const mgic_field *dpsi,
+                      const mgic_field *rhs, const mgic_field *psi, const mgic_field *phi,
+                      const double bh[13], const int *ref_ratio, int iter) {
   return guard([&] {
     need(dpsi, "dpsi");
     need(rhs, "rhs");
@@ -413,13 +421,51 @@ MGIC_IO_API int mgic_io_write_solver_data(const char *filename, int nlevels,
       need(psi[l], "psi[l]");
       need(dpsi[l], "dpsi[l]");
       need(rhs[l], "rhs[l]");
+      if (phi) need(phi[l], "phi[l]");
     }
     char name[64];
     std::snprintf(name, sizeof name, "vcPoissonOut.3d_%d.hdf5", iter);  // WriteOutput.H:63-70
     write_fields(filename ? filename : name, J, lead, [&](int l, int n, int k0, int nk, double *out) {
-      mg(mgic_field_solver_vars(dpsi[l], rhs[l], psi[l], n, k0, nk, bh, out, 0));
+      if (phi)
+        mg(mgic_field_solver_vars_phi(dpsi[l], rhs[l], psi[l], phi[l], n, k0, nk, bh, out, 0));
+      else
+        mg(mgic_field_solver_vars(dpsi[l], rhs[l], psi[l], n, k0, nk, bh, out, 0));
     });
   });
+}
+
+}  // namespace
+
+extern "C" {
+
+MGIC_IO_API int mgic_io_write_final_data(const char *filename, int nlevels, const mgic_field *psi,
+                                         const double bh[13], int max_level,
+                                         const int *ref_ratio) {
+  return write_final_data(filename, nlevels, psi, nullptr, bh, max_level, ref_ratio);
+}
+
+MGIC_IO_API int mgic_io_write_final_data_phi(const char *filename, int nlevels,
+                                             const mgic_field *psi, const mgic_field *phi,
+                                             const double bh[13], int max_level,
+                                             const int *ref_ratio) {
+  if (!phi) return guard([&] { need(phi, "phi"); });
+  return write_final_data(filename, nlevels, psi, phi, bh, max_level, ref_ratio);
+}
+
+MGIC_IO_API int mgic_io_write_solver_data(const char *filename, int nlevels,
+                                          const mgic_field *dpsi, const mgic_field *rhs,
+                                          const mgic_field *psi, const double bh[13],
+                                          const int *ref_ratio, int iter) {
+  return write_solver_data(filename, nlevels, dpsi, rhs, psi, nullptr, bh, ref_ratio, iter);
+}
+
+MGIC_IO_API int mgic_io_write_solver_data_phi(const char *filename, int nlevels,
+                                              const mgic_field *dpsi, const mgic_field *rhs,
+                                              const mgic_field *psi, const mgic_field *phi,
+                                              const double bh[13], const int *ref_ratio,
+                                              int iter) {
+  if (!phi) return guard([&] { need(phi, "phi"); });
+  return write_solver_data(filename, nlevels, dpsi, rhs, psi, phi, bh, ref_ratio, iter);
 }
 
 MGIC_IO_API int mgic_io_write_host(const char *filename, int kind, int nlevels, const int *nbox,

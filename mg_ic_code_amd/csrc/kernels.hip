@@ -1179,6 +1179,190 @@ __global__ __launch_bounds__(256) void k_output_vars(double *__restrict__ out,
   for (int c = 0; c < 31; ++c) o[c * V] = v[c];
 }
 
+// ---- phi_0 as a stored field (the c_phi_0 component set_initial_conditions
+// fills, SetLevelData.cpp:32-71): one value per cell of the box grown by one,
+// the profile at that cell's centre (ghost cells outside the domain or under
+// a coarse-fine boundary included; never exchanged, BC-filled or
+// interpolated).  The generators below are the analytic ones above with
+// every bh_phi evaluation replaced by a load of the stored field; the
+// analytic kernels keep their own code, so that it does not move.
+//
+// PROFILE is a template parameter (no runtime switch in the kernel):
+// kPhiGaussian is bh_phi itself, kPhiSine the profile MyPhiFunction.H names
+// for periodic boxes (:18-20), in its order
+template <int PROFILE>
+__device__ double phi_profile(const BhParams &p, double x, double y, double z) {
+  if (PROFILE == kPhiGaussian) return bh_phi(p, x, y, z);
+  return p.phi_amplitude * (sin(2 * M_PI * x * p.phi_wavelength / p.domlen[0]) +
+                            sin(2 * M_PI * y * p.phi_wavelength / p.domlen[1]) +
+                            sin(2 * M_PI * z * p.phi_wavelength / p.domlen[2]));
+}
+
+// one launch over the box grown by one (the allocation has kGhost >= 1 layers)
+template <int PROFILE>
+__global__ __launch_bounds__(256) void k_fill_phi(double *__restrict__ phi, const BoxArgs g,
+                                                  double dx, const BhParams p) {
+  const int i = (int)(blockIdx.x * TX + threadIdx.x) - 1;
+  const int j = (int)(blockIdx.y * TY + threadIdx.y) - 1;
+  const int k = (int)blockIdx.z - 1;
+  if (i > g.nx || j > g.ny) return;
+  const double x = bh_loc(g.glo[0] + i, dx, p.domlen[0]);
+  const double y = bh_loc(g.glo[1] + j, dx, p.domlen[1]);
+  const double z = bh_loc(g.glo[2] + k, dx, p.domlen[2]);
+  phi[(long)i + (long)j * g.sy + (long)k * g.sz] = phi_profile<PROFILE>(p, x, y, z);
+}
+
+// GETRHOGRADPHIF of the stored field at one cell, in k_rho_grad_phi's order
+__device__ __forceinline__ double phi_rho_grad(const double *__restrict__ phi, long idx,
+                                               const BoxArgs &g, double dx) {
+  const long st[3] = {1, g.sy, g.sz};
+  double acc = 0.0;
+  for (int d0 = 0; d0 < 3; ++d0) {
+    const double dphidx = 0.5 / dx * (+phi[idx + st[d0]] - phi[idx - st[d0]]);
+    acc = acc + 0.5 * dphidx * dphidx;
+  }
+  return acc;
+}
+
+// the Bowen-York terms of one cell in the analytic kernels' expression order:
+// A_ij_0 (SetBinaryBH.H:24-82) and psi_bh (:85-99)
+struct BhBowenYork {
+  double A11, A12, A13, A22, A23, A33, psi_bh;
+};
+__device__ BhBowenYork bh_bowen_york(const BhParams &p, const int iv[3], double dx) {
+  double loc[3];
+  for (int d = 0; d < 3; ++d) loc[d] = bh_loc(iv[d], dx, p.domlen[d]);
+  double l1[3] = {loc[0] - p.off1, loc[1], loc[2]}, l2[3] = {loc[0] - p.off2, loc[1], loc[2]};
+  const double r1 = sqrt(l1[0] * l1[0] + l1[1] * l1[1] + l1[2] * l1[2]);
+  const double r2 = sqrt(l2[0] * l2[0] + l2[1] * l2[1] + l2[2] * l2[2]);
+  const double n1[3] = {l1[0] / r1, l1[1] / r1, l1[2] / r1};
+  const double n2[3] = {l2[0] / r2, l2[1] / r2, l2[2] / r2};
+  const double J1[3] = {0.0, 0.0, p.spin1}, J2[3] = {0.0, 0.0, p.spin2};
+  const double P1[3] = {0.0, p.mom1, 0.0}, P2[3] = {0.0, p.mom2, 0.0};
+  BhBowenYork c;
+  c.A11 = bh_Aij(0, 0, r1, r2, n1, n2, J1, J2, P1, P2);
+  c.A22 = bh_Aij(1, 1, r1, r2, n1, n2, J1, J2, P1, P2);
+  c.A33 = bh_Aij(2, 2, r1, r2, n1, n2, J1, J2, P1, P2);
+  c.A12 = bh_Aij(0, 1, r1, r2, n1, n2, J1, J2, P1, P2);
+  c.A13 = bh_Aij(0, 2, r1, r2, n1, n2, J1, J2, P1, P2);
+  c.A23 = bh_Aij(1, 2, r1, r2, n1, n2, J1, J2, P1, P2);
+  c.psi_bh = p.m1 / r1 + p.m2 / r2;
+  return c;
+}
+__device__ __forceinline__ double bh_A2(const BhBowenYork &c) {  // SetLevelData.cpp:312-317
+  return pow(c.A11, 2.0) + pow(c.A22, 2.0) + pow(c.A33, 2.0) + 2 * pow(c.A12, 2.0) +
+         2 * pow(c.A13, 2.0) + 2 * pow(c.A23, 2.0);
+}
+
+// k_binary_bh with phi_0 read from `phi` (with its ghost layer)
+template <bool INTEGRAND>
+__global__ __launch_bounds__(256) void k_binary_bh_phi(double *__restrict__ acoef,
+                                                       double *__restrict__ rhs,
+                                                       const double *__restrict__ psi,
+                                                       const double *__restrict__ phi,
+                                                       const BoxArgs g, double dx,
+                                                       const BhParams p) {
+  const int i = blockIdx.x * TX + threadIdx.x;
+  const int j = blockIdx.y * TY + threadIdx.y;
+  const int k = blockIdx.z;
+  if (i >= g.nx || j >= g.ny) return;
+  const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k};
+  const long idx = (long)i + (long)j * g.sy + (long)k * g.sz;
+  const double rho_grad = phi_rho_grad(phi, idx, g, dx);
+  const BhBowenYork c = bh_bowen_york(p, iv, dx);
+  const double A2 = bh_A2(c);
+  const double rho = 0.5 * 0.0 * 0.0 + 0.0;
+  const double K = INTEGRAND ? 0.0 : p.constant_K;
+  const double m = (2.0 / 3.0) * (K * K) - 16.0 * M_PI * p.G_Newton * rho;
+  const double psi_c = psi ? psi[idx] : 1.0;
+  const double psi_0 = psi_c + c.psi_bh;
+  double lap = 0.0;
+  const long st[3] = {1, g.sy, g.sz};
+  for (int d0 = 0; d0 < 3; ++d0) {
+    const double pm = psi ? psi[idx - st[d0]] : 1.0, pp = psi ? psi[idx + st[d0]] : 1.0;
+    lap = lap + 1.0 / dx / dx * (+1.0 * pm - 2.0 * psi_c + 1.0 * pp);
+  }
+  if (INTEGRAND) {
+    acoef[idx] = -1.5 * m + 1.5 * A2 * pow(psi_0, -12.0) +
+                 24.0 * M_PI * p.G_Newton * rho_grad * pow(psi_0, -4.0) +
+                 12.0 * lap * pow(psi_0, -5.0);
+    return;
+  }
+  acoef[idx] = -0.625 * m * pow(psi_0, 4.0) - A2 * pow(psi_0, -8.0) +
+               2.0 * M_PI * p.G_Newton * rho_grad;
+  rhs[idx] = 0.125 * m * pow(psi_0, 5.0) - 0.125 * A2 * pow(psi_0, -7.0) -
+             2.0 * M_PI * p.G_Newton * rho_grad * psi_0 - lap;
+}
+
+// k_regrid_condition with phi_0 read from `phi`
+__global__ __launch_bounds__(256) void k_regrid_condition_phi(double *__restrict__ out,
+                                                              const double *__restrict__ psi,
+                                                              const double *__restrict__ phi,
+                                                              const BoxArgs g, double dx,
+                                                              const BhParams p) {
+  const int i = blockIdx.x * TX + threadIdx.x;
+  const int j = blockIdx.y * TY + threadIdx.y;
+  const int k = blockIdx.z;
+  if (i >= g.nx || j >= g.ny) return;
+  const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k};
+  const long idx = (long)i + (long)j * g.sy + (long)k * g.sz;
+  const double rho_grad = phi_rho_grad(phi, idx, g, dx);
+  const BhBowenYork c = bh_bowen_york(p, iv, dx);
+  const double A2 = bh_A2(c);
+  const double rho = 0.5 * 0.0 * 0.0 + 0.0;
+  const double m = (2.0 / 3.0) * (0.0 * 0.0) - 16.0 * M_PI * p.G_Newton * rho;
+  const double psi_0 = (psi ? psi[idx] : 1.0) + c.psi_bh;
+  out[idx] = 1.5 * fabs(m) + 1.5 * A2 * pow(psi_0, -7.0) +
+             24.0 * M_PI * p.G_Newton * fabs(rho_grad) * pow(psi_0, 1.0) + log(psi_0);
+}
+
+// k_output_vars with phi (KIND 0, v[25]) / phi_0 (KIND 1) copied from `phi`
+template <int KIND>
+__global__ __launch_bounds__(256) void k_output_vars_phi(double *__restrict__ out,
+                                                         const double *__restrict__ psi,
+                                                         const double *__restrict__ dpsi,
+                                                         const double *__restrict__ rhs,
+                                                         const double *__restrict__ phi,
+                                                         const BoxArgs g, int k0, int nk,
+                                                         double dx, const BhParams p) {
+  const int i = blockIdx.x * TX + threadIdx.x;
+  const int j = blockIdx.y * TY + threadIdx.y;
+  const int k = blockIdx.z;
+  if (i >= g.nx || j >= g.ny) return;
+  const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k0 + k};
+  const BhBowenYork b = bh_bowen_york(p, iv, dx);
+  const long idx = (long)i + (long)j * g.sy + (long)(k0 + k) * g.sz;
+  const double phi0 = phi[idx];
+  const double psi_c = psi[idx];
+  const long V = (long)g.nx * g.ny * nk;
+  double *o = out + (long)i + (long)g.nx * (j + (long)g.ny * k);
+  if (KIND == 1) {
+    const double v[10] = {dpsi[idx], rhs[idx], psi_c, b.A11, b.A12, b.A13, b.A22, b.A23, b.A33,
+                          phi0};
+#pragma unroll
+    for (int c = 0; c < 10; ++c) o[c * V] = v[c];
+    return;
+  }
+  const double chi = pow(psi_c + b.psi_bh, -4.0);
+  const double factor = pow(chi, 1.5);
+  double v[31];
+#pragma unroll
+  for (int c = 0; c < 31; ++c) v[c] = 0.0;
+  v[1] = v[4] = v[6] = 1.0;
+  v[18] = 1.0;
+  v[7] = p.constant_K;
+  v[0] = chi;
+  v[25] = phi0;
+  v[8] = b.A11 * factor;
+  v[9] = b.A12 * factor;
+  v[10] = b.A13 * factor;
+  v[11] = b.A22 * factor;
+  v[12] = b.A23 * factor;
+  v[13] = b.A33 * factor;
+#pragma unroll
+  for (int c = 0; c < 31; ++c) o[c * V] = v[c];
+}
+
 inline dim3 grid_cells(int nx, int ny, int nz) {
   return dim3((unsigned)((nx + TX - 1) / TX), (unsigned)((ny + TY - 1) / TY), (unsigned)nz);
 }
@@ -2079,6 +2263,55 @@ void output_vars(int kind, double *out, const double *psi, const double *dpsi, c
   else
     k_output_vars<1><<<grid_cells(g.nx, g.ny, nk), kBlock, 0, st>>>(out, psi, dpsi, rhs, g, k0, nk,
                                                                     dx, p);
+  check_launch();
+}
+
+void fill_phi(int profile, double *phi, const BoxArgs &g, double dx, const BhParams &p,
+              hipStream_t st) {
+  if (profile != kPhiGaussian && profile != kPhiSine)
+    throw Error(kBadArg, "unknown phi profile " + std::to_string(profile));
+  if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
+  const dim3 grid = grid_cells(g.nx + 2, g.ny + 2, g.nz + 2);
+  if (profile == kPhiGaussian)
+    k_fill_phi<kPhiGaussian><<<grid, kBlock, 0, st>>>(phi, g, dx, p);
+  else
+    k_fill_phi<kPhiSine><<<grid, kBlock, 0, st>>>(phi, g, dx, p);
+  check_launch();
+}
+
+void binary_bh_coefs_phi(double *acoef, double *rhs, const double *psi, const double *phi,
+                         const BoxArgs &g, double dx, const BhParams &p, hipStream_t st) {
+  if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
+  k_binary_bh_phi<false><<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(acoef, rhs, psi, phi, g,
+                                                                           dx, p);
+  check_launch();
+}
+
+void constant_k_integrand_phi(double *out, const double *psi, const double *phi, const BoxArgs &g,
+                              double dx, const BhParams &p, hipStream_t st) {
+  if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
+  k_binary_bh_phi<true><<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(out, nullptr, psi, phi, g,
+                                                                          dx, p);
+  check_launch();
+}
+
+void regrid_condition_phi(double *out, const double *psi, const double *phi, const BoxArgs &g,
+                          double dx, const BhParams &p, hipStream_t st) {
+  if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
+  k_regrid_condition_phi<<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(out, psi, phi, g, dx, p);
+  check_launch();
+}
+
+void output_vars_phi(int kind, double *out, const double *psi, const double *dpsi,
+                     const double *rhs, const double *phi, const BoxArgs &g, int k0, int nk,
+                     double dx, const BhParams &p, hipStream_t st) {
+  if (g.nx <= 0 || g.ny <= 0 || nk <= 0) return;
+  if (kind == 0)
+    k_output_vars_phi<0><<<grid_cells(g.nx, g.ny, nk), kBlock, 0, st>>>(out, psi, dpsi, rhs, phi, g,
+                                                                        k0, nk, dx, p);
+  else
+    k_output_vars_phi<1><<<grid_cells(g.nx, g.ny, nk), kBlock, 0, st>>>(out, psi, dpsi, rhs, phi, g,
+                                                                        k0, nk, dx, p);
   check_launch();
 }
 

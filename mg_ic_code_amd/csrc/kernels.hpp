@@ -227,6 +227,22 @@ void rho_grad_phi(double *r, const double *phi, const BoxArgs &g, double dx, hip
 constexpr int kNumGRChomboVars = 31, kNumSolverVars = 10;
 void output_vars(int kind, double *out, const double *psi, const double *dpsi, const double *rhs,
                  const BoxArgs &g, int k0, int nk, double dx, const BhParams &p, hipStream_t st);
+// ---- phi_0 as a stored field (SetLevelData.cpp:32-71's c_phi_0): the profile
+// at every cell centre of the box grown by one; the generators above with
+// phi_0 loaded from `phi` (read with its one ghost layer next to each face)
+// instead of evaluated
+enum PhiProfile { kPhiGaussian = 0, kPhiSine = 1 };  // MyPhiFunction.H:14-15, :18-20
+void fill_phi(int profile, double *phi, const BoxArgs &g, double dx, const BhParams &p,
+              hipStream_t st);  // an unknown profile throws kBadArg
+void binary_bh_coefs_phi(double *acoef, double *rhs, const double *psi, const double *phi,
+                         const BoxArgs &g, double dx, const BhParams &p, hipStream_t st);
+void constant_k_integrand_phi(double *out, const double *psi, const double *phi, const BoxArgs &g,
+                              double dx, const BhParams &p, hipStream_t st);
+void regrid_condition_phi(double *out, const double *psi, const double *phi, const BoxArgs &g,
+                          double dx, const BhParams &p, hipStream_t st);
+void output_vars_phi(int kind, double *out, const double *psi, const double *dpsi,
+                     const double *rhs, const double *phi, const BoxArgs &g, int k0, int nk,
+                     double dx, const BhParams &p, hipStream_t st);
 // x += y over the valid box grown by `grow` (<= kGhost) cells
 void incr_grown(double *x, const double *y, const BoxArgs &g, int grow, hipStream_t st);
 

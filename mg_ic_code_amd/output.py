@@ -8,8 +8,11 @@ libmgic_io.so (include/mgic_io.h).
 
 The per-box components are computed on the GPU (k_output_vars) and streamed
 into the file in z-slabs; there is no host fallback.  The multigrid_vars
-A_ij_0 and phi_0 are not stored fields here: set_initial_conditions sets them
+A_ij_0 are not stored fields here: set_initial_conditions sets them
 analytically and nothing changes them, so the kernels evaluate them in place.
+phi_0 is evaluated in place too (the Gaussian of MyPhiFunction.H) unless the
+caller passes the stored field (`phi`, one LevelData per level; phi.py): then
+the "phi" / "phi_0" component is copied from it.
 """
 from __future__ import annotations
 
@@ -43,11 +46,17 @@ def _enc(filename: Optional[str]):
 
 def output_final_data(psi: Sequence[LevelData], bh: dict, max_level: int = 0,
                       ref_ratio: Optional[Sequence[int]] = None,
-                      filename: Optional[str] = None) -> None:
+                      filename: Optional[str] = None,
+                      phi: Optional[Sequence[LevelData]] = None) -> None:
     """output_final_data (WriteOutput.H:127-227); constant_K = bh['constant_K'].
-    filename None: "vcPoissonFinal.3d.hdf5" in the working directory."""
+    filename None: "vcPoissonFinal.3d.hdf5" in the working directory.
+    phi: the stored phi_0 per level (None: the analytic Gaussian)."""
     n = len(psi)
     rr = list(ref_ratio) if ref_ratio is not None else [2] * n
+    if phi is not None:
+        io_call("mgic_io_write_final_data_phi", _enc(filename), n, _handles(psi), _handles(phi),
+                _bh(bh), int(max_level), (ctypes.c_int * n)(*rr))
+        return
     io_call("mgic_io_write_final_data", _enc(filename), n, _handles(psi), _bh(bh), int(max_level),
             (ctypes.c_int * n)(*rr))
 
@@ -55,29 +64,38 @@ def output_final_data(psi: Sequence[LevelData], bh: dict, max_level: int = 0,
 def output_solver_data(dpsi: Sequence[LevelData], rhs: Sequence[LevelData],
                        psi: Sequence[LevelData], bh: dict, iteration: int,
                        ref_ratio: Optional[Sequence[int]] = None,
-                       filename: Optional[str] = None) -> None:
+                       filename: Optional[str] = None,
+                       phi: Optional[Sequence[LevelData]] = None) -> None:
     """output_solver_data (WriteOutput.H:52-123) for NL iteration `iteration`.
-    filename None: "vcPoissonOut.3d_<iteration>.hdf5"."""
+    filename None: "vcPoissonOut.3d_<iteration>.hdf5".
+    phi: the stored phi_0 per level (None: the analytic Gaussian)."""
     n = len(psi)
     rr = list(ref_ratio) if ref_ratio is not None else [2] * n
+    if phi is not None:
+        io_call("mgic_io_write_solver_data_phi", _enc(filename), n, _handles(dpsi), _handles(rhs),
+                _handles(psi), _handles(phi), _bh(bh), (ctypes.c_int * n)(*rr), int(iteration))
+        return
     io_call("mgic_io_write_solver_data", _enc(filename), n, _handles(dpsi), _handles(rhs),
             _handles(psi), _bh(bh), (ctypes.c_int * n)(*rr), int(iteration))
 
 
 def grchombo_vars(psi: LevelData, n: int, bh: dict, k0: int = 0, nk: Optional[int] = None,
-                  out_device_ptr: Optional[int] = None) -> Optional[np.ndarray]:
+                  out_device_ptr: Optional[int] = None,
+                  phi: Optional[LevelData] = None) -> Optional[np.ndarray]:
     """set_output_data for local box n, planes [k0, k0+nk): (31, nk, ny, nx) on
-    the host, or written to device memory at out_device_ptr (returns None)."""
-    return _vars(0, psi, None, None, n, bh, k0, nk, out_device_ptr)
+    the host, or written to device memory at out_device_ptr (returns None).
+    phi: the stored phi_0 (None: the analytic Gaussian)."""
+    return _vars(0, psi, None, None, n, bh, k0, nk, out_device_ptr, phi)
 
 
 def solver_vars(dpsi: LevelData, rhs: LevelData, psi: LevelData, n: int, bh: dict, k0: int = 0,
-                nk: Optional[int] = None, out_device_ptr: Optional[int] = None):
+                nk: Optional[int] = None, out_device_ptr: Optional[int] = None,
+                phi: Optional[LevelData] = None):
     """output_solver_data's 10 components for local box n: (10, nk, ny, nx)."""
-    return _vars(1, psi, dpsi, rhs, n, bh, k0, nk, out_device_ptr)
+    return _vars(1, psi, dpsi, rhs, n, bh, k0, nk, out_device_ptr, phi)
 
 
-def _vars(kind, psi, dpsi, rhs, n, bh, k0, nk, dev):
+def _vars(kind, psi, dpsi, rhs, n, bh, k0, nk, dev, phi=None):
     lo, hi = psi.grid.local_box(n)[:3], psi.grid.local_box(n)[3:]
     nx, ny, nz = (hi[d] - lo[d] + 1 for d in range(3))
     nk = nz - k0 if nk is None else nk
@@ -87,7 +105,13 @@ def _vars(kind, psi, dpsi, rhs, n, bh, k0, nk, dev):
     else:
         out = np.empty((nc, nk, ny, nx))
         ptr = out.ctypes.data_as(ctypes.c_void_p)
-    if kind == 0:
+    if phi is not None and kind == 0:
+        call("mgic_field_grchombo_vars_phi", psi.handle, phi.handle, n, k0, nk, _bh(bh), ptr,
+             int(dev is not None))
+    elif phi is not None:
+        call("mgic_field_solver_vars_phi", dpsi.handle, rhs.handle, psi.handle, phi.handle, n, k0,
+             nk, _bh(bh), ptr, int(dev is not None))
+    elif kind == 0:
         call("mgic_field_grchombo_vars", psi.handle, n, k0, nk, _bh(bh), ptr, int(dev is not None))
     else:
         call("mgic_field_solver_vars", dpsi.handle, rhs.handle, psi.handle, n, k0, nk, _bh(bh), ptr,

@@ -1,0 +1,452 @@
+"""phi_0 as a stored device field (mg_ic_code_amd/phi.py; the c_phi_0 component
+of set_initial_conditions, SetLevelData.cpp:32-71).
+
+1. the fill kernels against the analytic path's phi_0 and the numpy formulas;
+2. the pin: with phi_0 filled by the Gaussian kernel every stored-field
+   generator gives the analytic entry point's bits;
+3. any stored field: acoef is 2 pi G GETRHOGRADPHIF(stored values), ghosts
+   read as stored;
+4. poisson_solve / set_grids with PhiProfile.gaussian() against today's path;
+5. the sine profile on a periodic box against the oracle loop fed by the
+   numpy restatement of tests/phi_ref.py (checked on the CPU first);
+6. the HDF5 writers; 7. errors; 8. the command line.
+
+Layouts: the smallest at which indexing can go wrong -- a ragged single box,
+2 x 2 x 1 boxes (non-zero glo, several boxes per rank), a 16^3 base with a
+16^3 level-1 patch (dx halved, ghosts under a coarse-fine boundary) and a
+periodic 16^3 base.
+"""
+import ctypes
+import dataclasses
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import oracle
+from tests import h5read, phi_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PARAMS = os.path.join(ROOT, "tests", "golden", "params.txt")
+
+# a wide Gaussian and G_Newton = 4: the rho_grad terms are of the order of the
+# others (asserted in the pin); no cell centre sits on a puncture
+L = 16.0
+BH = dict(domain_length=L, G_Newton=4.0, phi_amplitude=0.3, phi_wavelength=20.0,
+          bh1_bare_mass=0.5, bh2_bare_mass=0.3, bh1_spin=0.1, bh2_spin=-0.2, bh1_offset=2.1,
+          bh2_offset=-1.9, bh1_momentum=0.15, bh2_momentum=-0.05, constant_K=-0.3)
+BH_SINE = dict(BH, phi_wavelength=2.0)
+# test 3: no punctures, K = 0 -- A2, psi_bh and m vanish exactly
+BH_BARE = dict(BH_SINE, bh1_bare_mass=0.0, bh2_bare_mass=0.0, bh1_spin=0.0, bh2_spin=0.0,
+               bh1_momentum=0.0, bh2_momentum=0.0, constant_K=0.0)
+
+LAYOUTS = ["ragged", "2x2x1", "base+patch", "periodic"]
+
+
+def _shape(b, g=0):
+    return (b[5] - b[2] + 1 + 2 * g, b[4] - b[1] + 1 + 2 * g, b[3] - b[0] + 1 + 2 * g)
+
+
+def _grids(comm, layout):
+    """The level grids of a layout (coarsest first)."""
+    import mg_ic_code_amd as mg
+    from mg_ic_code_amd.decomposition import split_domain
+    if layout == "ragged":
+        dom = (0, 0, 0, 19, 11, 9)
+        return [mg.Grid(comm, dom, [dom], L / 20)]
+    if layout == "2x2x1":
+        dom = (0, 0, 0, 31, 15, 7)
+        return [mg.Grid(comm, dom, split_domain(dom, (2, 2, 1)), L / 32)]
+    dom = (0, 0, 0, 15, 15, 15)
+    if layout == "periodic":
+        return [mg.Grid(comm, dom, [dom], L / 16, periodic=(1, 1, 1))]
+    assert layout == "base+patch"
+    return [mg.Grid(comm, dom, [dom], L / 16),
+            mg.Grid(comm, (0, 0, 0, 31, 31, 31), [(8, 8, 8, 23, 23, 23)], L / 32, patches=True)]
+
+
+def _bhv(bh):
+    from mg_ic_code_amd.core import BH_KEYS
+    return (ctypes.c_double * 13)(*[float(bh[k]) for k in BH_KEYS])
+
+
+def _boxes(grid):
+    return [grid.local_box(n) for n in range(grid.num_local)]
+
+
+def _all(field, with_ghosts=False):
+    return [field.download(n, with_ghosts=with_ghosts) for n in range(field.grid.num_local)]
+
+
+def _same(xs, ys):
+    return all(np.array_equal(x, y) for x, y in zip(xs, ys))
+
+
+# ------------------------------------------------------------------ CPU
+def test_restatement_matches_oracle_analytic_generator_on_the_gaussian():
+    # tests/phi_ref.py given the Gaussian against the oracle's own analytic
+    # set_a_coef / set_rhs / integrand, to 1e-13: relative for aCoef; rhs and
+    # the integrand change sign inside the boxes, so there 1e-13 of the
+    # field's largest magnitude
+    rng = np.random.default_rng(5)
+    for lo, hi, dx in (((0, 0, 0), (19, 11, 9), L / 20), ((16, 8, 0), (31, 15, 7), L / 32),
+                       ((8, 8, 8), (23, 23, 23), L / 32)):
+        pg = phi_ref.phi_on_box(phi_ref.gaussian, BH, lo, hi, dx)
+        for psi in (None, 1.0 + 0.05 * rng.uniform(-1, 1, _shape(lo + hi, 1))):
+            a, r = phi_ref.nl_coefs_phi(BH, lo, hi, dx, psi, pg)
+            ao, ro = oracle.nl_coefs(BH, lo, hi, dx, psi)
+            np.testing.assert_allclose(a, ao, rtol=1e-13, atol=0)
+            np.testing.assert_allclose(r, ro, rtol=0, atol=1e-13 * np.abs(ro).max())
+            if psi is not None:
+                i1 = phi_ref.nl_integrand_phi(BH, lo, hi, dx, psi, pg)
+                io = oracle.nl_integrand(BH, lo, hi, dx, psi)
+                np.testing.assert_allclose(i1, io, rtol=0, atol=1e-13 * np.abs(io).max())
+
+
+def test_unknown_profile_name_and_bad_phi0_are_refused_on_the_host():
+    from mg_ic_code_amd import MgicError
+    from mg_ic_code_amd.grids import set_grids
+    from mg_ic_code_amd.params import read_params_file
+    from mg_ic_code_amd.phi import PhiProfile
+    with pytest.raises(ValueError):
+        PhiProfile("square")
+    with pytest.raises(TypeError):
+        PhiProfile.from_function(3.0)
+    # set_grids takes a profile only (levels appear and must be filled): refused
+    # with the library's bad-argument error before a grid or a field is touched
+    with pytest.raises(MgicError) as ei:
+        set_grids(None, read_params_file(PARAMS), None, phi0=[object()])
+    assert ei.value.code == -1 and "PhiProfile" in str(ei.value)
+
+
+# ------------------------------------------------------------------ GPU
+@pytest.fixture(scope="module")
+def comm():
+    import mg_ic_code_amd as mg
+    return mg.Comm()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_fill_matches_analytic_phi0_and_numpy(comm, layout):
+    import mg_ic_code_amd as mg
+    from mg_ic_code_amd.output import solver_vars
+    from mg_ic_code_amd.phi import PhiProfile
+    for grid in _grids(comm, layout):
+        gauss = PhiProfile.gaussian().fill(grid, BH)
+        sine = PhiProfile.sine().fill(grid, BH_SINE)
+        psi = mg.LevelData(grid)
+        psi.set_val_all(1.0)
+        for n, b in enumerate(_boxes(grid)):
+            g = gauss.download(n, with_ghosts=True)
+            # interior: the bits of today's phi_0 component
+            assert np.array_equal(g[1:-1, 1:-1, 1:-1], solver_vars(psi, psi, psi, n, BH)[9])
+            # interior and ghosts (outside the domain / under the coarse-fine
+            # boundary too): the profile at the cell centre
+            ref = phi_ref.phi_on_box(phi_ref.gaussian, BH, b[:3], b[3:], grid.dx)
+            err = np.max(np.abs(g - ref) / np.abs(ref))
+            print(layout, b, "gaussian max rel err", err)
+            assert err <= 1e-13
+            s = sine.download(n, with_ghosts=True)
+            ref = phi_ref.phi_on_box(phi_ref.sine, BH_SINE, b[:3], b[3:], grid.dx)
+            err = np.max(np.abs(s - ref))
+            print(layout, b, "sine max abs err", err)
+            assert err <= 3 * BH_SINE["phi_amplitude"] * 1e-13
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_psi", [False, True], ids=["psi=None", "psi=random"])
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_stored_gaussian_path_is_bit_identical_to_analytic_path(comm, layout, with_psi):
+    import mg_ic_code_amd as mg
+    from mg_ic_code_amd._lib import call
+    from mg_ic_code_amd.grids import set_regrid_condition
+    from mg_ic_code_amd.output import grchombo_vars, solver_vars
+    from mg_ic_code_amd.phi import (PhiProfile, set_nl_coefs_phi, set_nl_integrand_phi,
+                                    set_regrid_condition_phi)
+    rng = np.random.default_rng(20261019)
+    for grid in _grids(comm, layout):
+        phi = PhiProfile.gaussian().fill(grid, BH)
+        psi = None
+        ones = mg.LevelData(grid)
+        ones.set_val_all(1.0)
+        if with_psi:
+            psi = mg.LevelData(grid)
+            for n, b in enumerate(_boxes(grid)):
+                psi.upload(n, 1.0 + 0.05 * rng.uniform(-1, 1, _shape(b, 1)), with_ghosts=True)
+        dpsi, rh = mg.LevelData(grid), mg.LevelData(grid)
+        for n, b in enumerate(_boxes(grid)):
+            dpsi.upload(n, rng.uniform(-1, 1, _shape(b)))
+            rh.upload(n, rng.uniform(-1, 1, _shape(b)))
+        a0, r0, a1, r1, a2 = (mg.LevelData(grid) for _ in range(5))
+        mg.set_nl_coefs(psi, a0, r0, BH)
+        set_nl_coefs_phi(psi, phi, a1, r1, BH)
+        assert _same(_all(a0), _all(a1)) and _same(_all(r0), _all(r1))
+        # the rho_grad terms are not negligible: without them acoef changes
+        mg.set_nl_coefs(psi, a2, r1, dict(BH, phi_amplitude=0.0))
+        rel = max(np.max(np.abs(x - y) / np.abs(x)) for x, y in zip(_all(a0), _all(a2)))
+        assert rel > 0.1, rel
+        call("mgic_field_nl_integrand", psi.handle if psi else None, a0.handle, _bhv(BH))
+        set_nl_integrand_phi(psi, phi, a1, BH)
+        assert _same(_all(a0), _all(a1))
+        set_regrid_condition(psi, a0, BH)
+        set_regrid_condition_phi(psi, phi, a1, BH)
+        assert _same(_all(a0), _all(a1))
+        u = psi if psi is not None else ones
+        for n in range(grid.num_local):
+            assert np.array_equal(grchombo_vars(u, n, BH), grchombo_vars(u, n, BH, phi=phi))
+            assert np.array_equal(solver_vars(dpsi, rh, u, n, BH),
+                                  solver_vars(dpsi, rh, u, n, BH, phi=phi))
+            # a z-slab of the stored-field components is that slab of the box
+            nz = _shape(grid.local_box(n))[0]
+            assert np.array_equal(grchombo_vars(u, n, BH, 3, nz - 4, phi=phi),
+                                  grchombo_vars(u, n, BH)[:, 3:nz - 1])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_any_stored_field_acoef_is_rho_grad_of_the_stored_values(comm, layout):
+    # no punctures, K = 0: acoef = ((2 pi) G) * GETRHOGRADPHIF(phi as stored).
+    # The random field's ghosts are what was uploaded, so they are read as
+    # stored, not re-evaluated.
+    import mg_ic_code_amd as mg
+    from mg_ic_code_amd.phi import PhiProfile, set_nl_coefs_phi
+    rng = np.random.default_rng(7)
+
+    def random_field(x, y, z):
+        return rng.uniform(-1, 1, (z.size, y.size, x.size))
+
+    for grid in _grids(comm, layout):
+        for prof in (PhiProfile.sine(), PhiProfile.from_function(random_field)):
+            phi = prof.fill(grid, BH_BARE)
+            a, r = mg.LevelData(grid), mg.LevelData(grid)
+            set_nl_coefs_phi(None, phi, a, r, BH_BARE)
+            for n, b in enumerate(_boxes(grid)):
+                pg = phi.download(n, with_ghosts=True)
+                want = ((2.0 * np.pi) * BH_BARE["G_Newton"]) * oracle.getrhogradphif(
+                    pg, b[:3], b[3:], grid.dx)
+                assert np.any(want != 0.0)
+                assert np.array_equal(a.download(n), want), (layout, prof, b)
+
+
+def _wide_gaussian_prm(**kw):
+    # params.txt with a Gaussian as wide as the box (wavelength 1 in a box of
+    # 100 is zero to rounding outside the centre cells)
+    from mg_ic_code_amd.params import read_params_file
+    return dataclasses.replace(read_params_file(PARAMS), phi_wavelength=400.0, **kw)
+
+
+def _solve(grid, prm, **kw):
+    from mg_ic_code_amd.nl import NLDivergenceError, poisson_solve
+    try:
+        return poisson_solve(grid, prm, max_depth=2, max_NL_iterations=2, **kw)
+    except NLDivergenceError as e:  # |dpsi| > 1e-1 after two steps: the state travels with it
+        return e.result
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["one level", "base+patch", "periodic"])
+def test_solve_with_stored_gaussian_is_bit_identical(comm, case):
+    import mg_ic_code_amd as mg
+    from mg_ic_code_amd.phi import PhiProfile
+    prm = _wide_gaussian_prm(is_periodic=int(case == "periodic"))
+    dom = (0, 0, 0, 15, 15, 15)
+    dx = prm.domainLength[0] / 16
+    grids = [mg.Grid(comm, dom, [dom], dx, periodic=(1, 1, 1) if case == "periodic" else (0, 0, 0))]
+    if case == "base+patch":
+        grids.append(mg.Grid(comm, (0, 0, 0, 31, 31, 31), [(8, 8, 8, 23, 23, 23)], dx / 2,
+                             patches=True))
+    arg = grids if len(grids) > 1 else grids[0]
+    ref = _solve(arg, prm)
+    got = _solve(arg, prm, phi0=PhiProfile.gaussian())
+    # the pre-filled form: one LevelData per level
+    pre = _solve(arg, prm, phi0=[PhiProfile.gaussian().fill(g, prm) for g in grids])
+    for res in (got, pre):
+        assert res.linear_iterations == ref.linear_iterations and len(ref.linear_iterations) == 2
+        assert res.dpsi_norms == ref.dpsi_norms
+        assert res.constant_K == ref.constant_K
+        assert (len(ref.constant_K) == 2) == (case == "periodic")
+        for l in range(len(grids)):
+            p0 = ref.psi[l] if len(grids) > 1 else ref.psi
+            p1 = res.psi[l] if len(grids) > 1 else res.psi
+            assert _same(_all(p0, True), _all(p1, True))
+    assert np.all(np.isfinite(ref.dpsi_norms))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("wavelength", ["1", "400"])
+def test_set_grids_with_stored_gaussian_returns_the_same_boxes(comm, wavelength):
+    # the off-centre-hole deck of tests/test_regrid.py (one hole at x = +10) at
+    # a 16^3 base; once more with a Gaussian wide enough to reach the tags
+    import mg_ic_code_amd as mg
+    from mg_ic_code_amd.grids import set_grids
+    from mg_ic_code_amd.params import read_params_file
+    from mg_ic_code_amd.phi import PhiProfile
+    prm = read_params_file(PARAMS, overrides=dict(
+        bh1_offset="10.0", bh2_bare_mass="0.0", bh2_spin="0.0", bh2_momentum="0.0",
+        block_factor="8", max_grid_size="16", fill_ratio="0.5", phi_wavelength=wavelength))
+    dom0 = (0, 0, 0, 15, 15, 15)
+    base = mg.Grid(comm, dom0, [dom0], prm.L / 16)
+    ref = set_grids(comm, prm, base, max_level=2)
+    got = set_grids(comm, prm, base, max_level=2, phi0=PhiProfile.gaussian())
+    assert len(ref) >= 2
+    assert [g.boxes for g in got] == [g.boxes for g in ref]
+    assert [g.domain for g in got] == [g.domain for g in ref]
+
+
+# test 5: params.txt (G_Newton = 1, phi_amplitude = 0.1) made periodic, with
+# phi_wavelength = 1: one sine period per direction.  On the oracle alone
+# these values give linear iteration counts [2, 2] that stay [2, 2] when aCoef
+# and rhs are perturbed by 1e-13 relative (checked below, no GPU), and the
+# sine carries the solution: K = -0.0440 against -0.00028 with phi = 0.
+def _sine_case():
+    from mg_ic_code_amd.params import read_params_file
+    prm = dataclasses.replace(read_params_file(PARAMS), is_periodic=1, phi_wavelength=1.0)
+    assert (prm.G_Newton, prm.phi_amplitude) == (1.0, 0.1)
+    n = 16
+    pg = phi_ref.phi_on_box(phi_ref.sine, prm.bh(), (0, 0, 0), (n - 1,) * 3,
+                            prm.domainLength[0] / n)
+    return prm, n, pg
+
+
+_SINE_REF = {}
+
+
+def _sine_reference():
+    if not _SINE_REF:
+        prm, n, pg = _sine_case()
+        _SINE_REF["r"] = phi_ref.oracle_poisson_solve_phi(prm, n, max_depth=2, n_nl=2, phi_g=pg)
+    return _SINE_REF["r"]
+
+
+def test_sine_reference_iteration_counts_are_insensitive_to_rounding():
+    prm, n, pg = _sine_case()
+    _, norms, iters, ks = _sine_reference()
+    assert iters == [2, 2] and norms[1] < 1e-2 * norms[0]
+    pert = 1e-13 * np.random.default_rng(3).uniform(-1, 1, (n, n, n))
+    for p in (pert, -pert):
+        _, norms_p, iters_p, ks_p = phi_ref.oracle_poisson_solve_phi(prm, n, 2, 2, pg, perturb=p)
+        assert iters_p == iters
+        np.testing.assert_allclose(norms_p, norms, rtol=1e-9)
+        np.testing.assert_allclose(ks_p, ks, rtol=1e-9)
+
+
+@pytest.mark.gpu
+def test_periodic_sine_solve_matches_oracle(comm, tmp_path):
+    import mg_ic_code_amd as mg
+    from mg_ic_code_amd.nl import poisson_solve
+    from mg_ic_code_amd.phi import PhiProfile
+    prm, n, _ = _sine_case()
+    dom = (0, 0, 0, n - 1, n - 1, n - 1)
+    grid = mg.Grid(comm, dom, [dom], prm.domainLength[0] / n, periodic=(1, 1, 1))
+    res = poisson_solve(grid, prm, max_depth=2, max_NL_iterations=2, phi0=PhiProfile.sine(),
+                        output_dir=str(tmp_path))
+    psi_o, norms_o, iters_o, ks_o = _sine_reference()
+    print("iterations", res.linear_iterations, iters_o, "norms", res.dpsi_norms, norms_o,
+          "K", res.constant_K, ks_o)
+    assert res.linear_iterations == iters_o
+    np.testing.assert_allclose(res.dpsi_norms, norms_o, rtol=1e-6)
+    np.testing.assert_allclose(res.constant_K, ks_o, rtol=1e-6)
+    g = res.psi.download(0)
+    c = psi_o[1:-1, 1:-1, 1:-1]
+    err = np.linalg.norm(g - c) / np.linalg.norm(c)
+    print("psi rel-L2", err)
+    assert err <= 1e-10
+    # the loop's files carry the stored field (phi = component 25 of 31, phi_0 = 9 of 10)
+    want = PhiProfile.sine().fill(grid, prm).download(0)
+    for name, nc, comp in (("vcPoissonFinal.3d.hdf5", 31, 25), ("vcPoissonOut.3d_1.hdf5", 10, 9)):
+        data = h5read.dataset(str(tmp_path / name), "/level_0/data:datatype=0", "<f8")
+        assert np.array_equal(data.reshape((nc, n, n, n))[comp], want)
+
+
+@pytest.mark.gpu
+def test_output_files_carry_the_stored_field(comm, tmp_path):
+    import mg_ic_code_amd as mg
+    from mg_ic_code_amd.phi import PhiProfile
+    rng = np.random.default_rng(12)
+    grids = _grids(comm, "base+patch")
+    psi, dpsi, rhs, phi = [], [], [], []
+    for g in grids:
+        u, d, r = (mg.LevelData(g) for _ in range(3))
+        for n, b in enumerate(_boxes(g)):
+            u.upload(n, 1.0 + 0.05 * rng.uniform(-1, 1, _shape(b)))
+            d.upload(n, rng.uniform(-1, 1, _shape(b)))
+            r.upload(n, rng.uniform(-1, 1, _shape(b)))
+        psi.append(u)
+        dpsi.append(d)
+        rhs.append(r)
+        phi.append(PhiProfile.sine().fill(g, BH_SINE))
+    names = {k: str(tmp_path / f"{k}.hdf5") for k in ("f_a", "f_s", "s_a", "s_s")}
+    mg.output_final_data(psi, BH_SINE, 1, [2, 2], names["f_a"])
+    mg.output_final_data(psi, BH_SINE, 1, [2, 2], names["f_s"], phi=phi)
+    mg.output_solver_data(dpsi, rhs, psi, BH_SINE, 3, [2, 2], names["s_a"])
+    mg.output_solver_data(dpsi, rhs, psi, BH_SINE, 3, [2, 2], names["s_s"], phi=phi)
+    for analytic, stored, nc, comp in ((names["f_a"], names["f_s"], 31, 25),
+                                       (names["s_a"], names["s_s"], 10, 9)):
+        assert h5read.contents(analytic) == h5read.contents(stored)
+        for l, g in enumerate(grids):
+            shape = (nc,) + _shape(g.boxes[0])
+            da = h5read.dataset(analytic, f"/level_{l}/data:datatype=0", "<f8").reshape(shape)
+            ds = h5read.dataset(stored, f"/level_{l}/data:datatype=0", "<f8").reshape(shape)
+            assert np.array_equal(ds[comp], phi[l].download(0))
+            assert not np.array_equal(da[comp], ds[comp])
+            other = [c for c in range(nc) if c != comp]
+            assert np.array_equal(da[other], ds[other])
+            assert h5read.boxes(analytic, l) == h5read.boxes(stored, l)
+
+
+@pytest.mark.gpu
+def test_layout_mismatch_and_unknown_profile_raise_the_library_error(comm):
+    import mg_ic_code_amd as mg
+    from mg_ic_code_amd._lib import call
+    from mg_ic_code_amd.output import grchombo_vars
+    from mg_ic_code_amd.phi import (PhiProfile, set_nl_coefs_phi, set_nl_integrand_phi,
+                                    set_regrid_condition_phi)
+    g0, g1 = _grids(comm, "base+patch")
+    phi1 = PhiProfile.gaussian().fill(g1, BH)
+    a, r = mg.LevelData(g0), mg.LevelData(g0)
+    a.set_val(7.0)
+    for fn in (lambda: set_nl_coefs_phi(None, phi1, a, r, BH),
+               lambda: set_nl_integrand_phi(None, phi1, a, BH),
+               lambda: set_regrid_condition_phi(None, phi1, a, BH),
+               lambda: grchombo_vars(a, 0, BH, phi=phi1)):
+        with pytest.raises(mg.MgicError) as ei:
+            fn()
+        assert ei.value.code == -1 and "phi" in str(ei.value)
+    assert np.all(a.download(0) == 7.0)  # nothing was launched
+    with pytest.raises(mg.MgicError) as ei:
+        PhiProfile(7).fill(g0, BH)
+    assert ei.value.code == -1 and "unknown phi profile" in str(ei.value)
+    with pytest.raises(mg.MgicError) as ei:
+        call("mgic_field_fill_phi", None, 0, _bhv(BH))
+    assert "null argument" in str(ei.value)
+    with pytest.raises(mg.MgicError) as ei:
+        call("mgic_field_nl_coefs_phi", None, None, a.handle, r.handle, _bhv(BH))
+    assert "null argument" in str(ei.value)
+    with pytest.raises(mg.MgicError):  # one LevelData per level, not a wrong count
+        from mg_ic_code_amd.nl import poisson_solve
+        poisson_solve([g0, g1], _wide_gaussian_prm(), phi0=[phi1])
+
+
+@pytest.mark.gpu
+def test_run_poisson_cli_with_sine_profile(tmp_path):
+    deck = tmp_path / "periodic.txt"
+    with open(PARAMS) as f:
+        txt = f.read()
+    # three NL steps: the fourth |dpsi| (7e-9) is the linear solver's floor at
+    # tolerance 1e-10, after which BiCGStab takes no step and dpsi keeps its value
+    assert "is_periodic = 0" in txt and "max_NL_iterations = 6" in txt
+    deck.write_text(txt.replace("is_periodic = 0", "is_periodic = 1")
+                    .replace("max_NL_iterations = 6", "max_NL_iterations = 3"))
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "run_poisson.py"), str(deck),
+                          "--size", "16", "--max-depth", "2", "--phi", "sine"],
+                         capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    norms = [float(line.rsplit(" ", 1)[1]) for line in out.stdout.splitlines()
+             if line.startswith("Main Loop Iteration")]
+    print(out.stdout)
+    assert len(norms) == 3 and all(b < a for a, b in zip(norms, norms[1:])), norms
+    # the sine reference's first two steps (printed to 7 digits)
+    np.testing.assert_allclose(norms[:2], _sine_reference()[1], rtol=1e-5)

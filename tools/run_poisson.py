@@ -8,8 +8,13 @@ With --max-level K > 0 the AMR hierarchy is generated first as the reference's
 set_grids does (tagging on the regrid condition, up to K levels above the
 base), and the loop runs over it.
 
+With --phi gaussian|sine the scalar field phi_0 is stored on the device once
+(mg_ic_code_amd/phi.py) and read by the stored-field generators; without the
+flag phi_0 is the Gaussian evaluated in the kernels.  A deck with is_periodic
+set runs on a periodic base level.
+
 usage: python tools/run_poisson.py [params.txt] [--size N] [--boxes-per-rank x,y,z]
-                                   [--max-level K]
+                                   [--max-level K] [--phi gaussian|sine]
 """
 import argparse
 import json
@@ -29,6 +34,8 @@ def main():
     ap.add_argument("--max-depth", type=int, default=-1)
     ap.add_argument("--max-level", type=int, default=0,
                     help="generate up to K AMR levels above the base with set_grids (0: one level)")
+    ap.add_argument("--phi", choices=("gaussian", "sine"), default=None,
+                    help="store phi_0 on the device from this profile (default: analytic Gaussian)")
     args = ap.parse_args()
     import mg_ic_code_amd as mg
     from mg_ic_code_amd.decomposition import decompose
@@ -38,16 +45,18 @@ def main():
     n = args.size or prm.N[0]
     bpr = tuple(int(v) for v in args.boxes_per_rank.split(","))
     dom, boxes, owners = decompose((n, n, n), 1, boxes_per_rank=bpr)
-    grid = mg.Grid(mg.Comm(), dom, boxes, prm.domainLength[0] / n, owners=owners)
+    grid = mg.Grid(mg.Comm(), dom, boxes, prm.domainLength[0] / n,
+                   periodic=(1, 1, 1) if prm.is_periodic else (0, 0, 0), owners=owners)
     levels = grid
+    phi0 = mg.PhiProfile(args.phi) if args.phi else None
     if args.max_level > 0:
         from mg_ic_code_amd.grids import set_grids
-        levels = set_grids(grid.comm, prm, grid, max_level=args.max_level)
+        levels = set_grids(grid.comm, prm, grid, max_level=args.max_level, phi0=phi0)
         for lev, g in enumerate(levels):
             cells = sum((b[3] - b[0] + 1) * (b[4] - b[1] + 1) * (b[5] - b[2] + 1) for b in g.boxes)
             print(f"level {lev}: {len(g.boxes)} boxes, {cells} cells")
     t0 = time.perf_counter()
-    res = poisson_solve(levels, prm, max_depth=args.max_depth)
+    res = poisson_solve(levels, prm, max_depth=args.max_depth, phi0=phi0)
     mg.device_synchronize()
     dt = time.perf_counter() - t0
     for i, (nrm, it) in enumerate(zip(res.dpsi_norms, res.linear_iterations)):
