@@ -615,32 +615,44 @@ static kern::BhParams bh_params(const double bh[13]) {
   p.constant_K = bh[12];
   return p;
 }
+// The generators below take phi: the stored phi_0 (the *_phi entry points,
+// which refuse a null one first), or null: evaluated in place.
+static void nl_coefs_capi(mgic_field psi, mgic_field phi, mgic_field acoef, mgic_field rhs,
+                          const double bh[13]) {
+  NEED(acoef);
+  NEED(rhs);
+  NEED(bh);
+  const Grid &g = *acoef->f->grid;
+  if (psi) check_same_layout(g, *psi->f, "psi");
+  if (phi) check_same_layout(g, *phi->f, "phi");
+  check_same_layout(g, *rhs->f, "rhs");
+  const kern::BhParams p = bh_params(bh);
+  for (int n = 0; n < g.nlocal(); ++n)
+    kern::binary_bh_coefs(acoef->f->p[n], rhs->f->p[n], psi ? psi->f->p[n] : nullptr,
+                          phi ? phi->f->p[n] : nullptr, g.box_args_plain(n), g.dx, p,
+                          g.comm->stream());
+}
+// gen: kern::constant_k_integrand or kern::regrid_condition
+using PsiGenerator = void (*)(double *, const double *, const double *, const BoxArgs &, double,
+                              const kern::BhParams &, hipStream_t);
+static void psi_generator_capi(PsiGenerator gen, mgic_field psi, mgic_field phi, mgic_field out,
+                               const double bh[13]) {
+  NEED(out);
+  NEED(bh);
+  const Grid &g = *out->f->grid;
+  if (psi) check_same_layout(g, *psi->f, "psi");
+  if (phi) check_same_layout(g, *phi->f, "phi");
+  const kern::BhParams p = bh_params(bh);
+  for (int n = 0; n < g.nlocal(); ++n)
+    gen(out->f->p[n], psi ? psi->f->p[n] : nullptr, phi ? phi->f->p[n] : nullptr,
+        g.box_args_plain(n), g.dx, p, g.comm->stream());
+}
 MGIC_API int mgic_field_nl_coefs(mgic_field psi, mgic_field acoef, mgic_field rhs,
                                  const double bh[13]) {
-  return guard([&] {
-    NEED(acoef);
-    NEED(rhs);
-    NEED(bh);
-    const Grid &g = *acoef->f->grid;
-    if (psi) check_same_layout(g, *psi->f, "psi");
-    check_same_layout(g, *rhs->f, "rhs");
-    const kern::BhParams p = bh_params(bh);
-    for (int n = 0; n < g.nlocal(); ++n)
-      kern::binary_bh_coefs(acoef->f->p[n], rhs->f->p[n], psi ? psi->f->p[n] : nullptr,
-                            g.box_args_plain(n), g.dx, p, g.comm->stream());
-  });
+  return guard([&] { nl_coefs_capi(psi, nullptr, acoef, rhs, bh); });
 }
 MGIC_API int mgic_field_nl_integrand(mgic_field psi, mgic_field out, const double bh[13]) {
-  return guard([&] {
-    NEED(out);
-    NEED(bh);
-    const Grid &g = *out->f->grid;
-    if (psi) check_same_layout(g, *psi->f, "psi");
-    const kern::BhParams p = bh_params(bh);
-    for (int n = 0; n < g.nlocal(); ++n)
-      kern::constant_k_integrand(out->f->p[n], psi ? psi->f->p[n] : nullptr, g.box_args_plain(n),
-                                 g.dx, p, g.comm->stream());
-  });
+  return guard([&] { psi_generator_capi(kern::constant_k_integrand, psi, nullptr, out, bh); });
 }
 // ---- output: WriteOutput.H's per-box components, and
 // the layout queries the HDF5 writer (libmgic_io) needs
@@ -691,10 +703,7 @@ static void output_vars_capi(int kind, mgic_field psi, mgic_field dpsi, mgic_fie
   double *d = out;
   if (!on_device) d = static_cast<double *>(scratch_device(bytes));
   const double *dp = kind ? dpsi->f->p[n] : nullptr, *rp = kind ? rhs->f->p[n] : nullptr;
-  if (phi)
-    kern::output_vars_phi(kind, d, u.p[n], dp, rp, phi->f->p[n], a, k0, nk, g.dx, p, st);
-  else
-    kern::output_vars(kind, d, u.p[n], dp, rp, a, k0, nk, g.dx, p, st);
+  kern::output_vars(kind, d, u.p[n], dp, rp, phi ? phi->f->p[n] : nullptr, a, k0, nk, g.dx, p, st);
   if (!on_device) {
     MGIC_HIP(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, st));
     MGIC_HIP(hipStreamSynchronize(st));
@@ -711,16 +720,7 @@ MGIC_API int mgic_field_solver_vars(mgic_field dpsi, mgic_field rhs, mgic_field 
 // ---- set_grids (SetGrids.cpp:31-149): condition and tags on
 // the device, clustering on the host (regrid.cpp)
 MGIC_API int mgic_field_regrid_condition(mgic_field psi, mgic_field out, const double bh[13]) {
-  return guard([&] {
-    NEED(out);
-    NEED(bh);
-    const Grid &g = *out->f->grid;
-    if (psi) check_same_layout(g, *psi->f, "psi");
-    const kern::BhParams p = bh_params(bh);
-    for (int n = 0; n < g.nlocal(); ++n)
-      kern::regrid_condition(out->f->p[n], psi ? psi->f->p[n] : nullptr, g.box_args_plain(n), g.dx,
-                             p, g.comm->stream());
-  });
+  return guard([&] { psi_generator_capi(kern::regrid_condition, psi, nullptr, out, bh); });
 }
 // ---- phi_0 as a stored field (SetLevelData.cpp:32-71's c_phi_0): filled once
 // from a built-in profile (or uploaded by the caller), then read by the
@@ -741,47 +741,21 @@ MGIC_API int mgic_field_nl_coefs_phi(mgic_field psi, mgic_field phi, mgic_field 
                                      mgic_field rhs, const double bh[13]) {
   return guard([&] {
     NEED(phi);
-    NEED(acoef);
-    NEED(rhs);
-    NEED(bh);
-    const Grid &g = *acoef->f->grid;
-    if (psi) check_same_layout(g, *psi->f, "psi");
-    check_same_layout(g, *phi->f, "phi");
-    check_same_layout(g, *rhs->f, "rhs");
-    const kern::BhParams p = bh_params(bh);
-    for (int n = 0; n < g.nlocal(); ++n)
-      kern::binary_bh_coefs_phi(acoef->f->p[n], rhs->f->p[n], psi ? psi->f->p[n] : nullptr,
-                                phi->f->p[n], g.box_args_plain(n), g.dx, p, g.comm->stream());
+    nl_coefs_capi(psi, phi, acoef, rhs, bh);
   });
 }
 MGIC_API int mgic_field_nl_integrand_phi(mgic_field psi, mgic_field phi, mgic_field out,
                                          const double bh[13]) {
   return guard([&] {
     NEED(phi);
-    NEED(out);
-    NEED(bh);
-    const Grid &g = *out->f->grid;
-    if (psi) check_same_layout(g, *psi->f, "psi");
-    check_same_layout(g, *phi->f, "phi");
-    const kern::BhParams p = bh_params(bh);
-    for (int n = 0; n < g.nlocal(); ++n)
-      kern::constant_k_integrand_phi(out->f->p[n], psi ? psi->f->p[n] : nullptr, phi->f->p[n],
-                                     g.box_args_plain(n), g.dx, p, g.comm->stream());
+    psi_generator_capi(kern::constant_k_integrand, psi, phi, out, bh);
   });
 }
 MGIC_API int mgic_field_regrid_condition_phi(mgic_field psi, mgic_field phi, mgic_field out,
                                              const double bh[13]) {
   return guard([&] {
     NEED(phi);
-    NEED(out);
-    NEED(bh);
-    const Grid &g = *out->f->grid;
-    if (psi) check_same_layout(g, *psi->f, "psi");
-    check_same_layout(g, *phi->f, "phi");
-    const kern::BhParams p = bh_params(bh);
-    for (int n = 0; n < g.nlocal(); ++n)
-      kern::regrid_condition_phi(out->f->p[n], psi ? psi->f->p[n] : nullptr, phi->f->p[n],
-                                 g.box_args_plain(n), g.dx, p, g.comm->stream());
+    psi_generator_capi(kern::regrid_condition, psi, phi, out, bh);
   });
 }
 MGIC_API int mgic_field_grchombo_vars_phi(mgic_field psi, mgic_field phi, int n, int k0, int nk,

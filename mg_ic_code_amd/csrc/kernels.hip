@@ -899,32 +899,14 @@ __device__ double bh_Aij(int i, int j, double r1, double r2, const double *n1, c
   return Aij;
 }
 
-// set_a_coef + set_rhs (SetLevelData.cpp:73-127, :281-325); psi == nullptr:
-// psi = 1 everywhere (NL iteration 0), else psi read with its ghost layer
-// INTEGRAND: set_constant_K_integrand (SetLevelData.cpp:131-180) into acoef
-// instead (m taken at K = 0, rhs untouched)
-template <bool INTEGRAND>
-__global__ __launch_bounds__(256) void k_binary_bh(double *__restrict__ acoef,
-                                                   double *__restrict__ rhs,
-                                                   const double *__restrict__ psi,
-                                                   const BoxArgs g, double dx, const BhParams p) {
-  const int i = blockIdx.x * TX + threadIdx.x;
-  const int j = blockIdx.y * TY + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i >= g.nx || j >= g.ny) return;
-  const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k};
+// the Bowen-York terms of one cell: A_ij_0 (SetBinaryBH.H:24-82) and psi_bh
+// (:85-99)
+struct BhBowenYork {
+  double A11, A12, A13, A22, A23, A33, psi_bh;
+};
+__device__ BhBowenYork bh_bowen_york(const BhParams &p, const int iv[3], double dx) {
   double loc[3];
   for (int d = 0; d < 3; ++d) loc[d] = bh_loc(iv[d], dx, p.domlen[d]);
-  double rho_grad = 0.0;  // GETRHOGRADPHIF, SetLevelDataF.ChF:65-103
-  for (int d0 = 0; d0 < 3; ++d0) {
-    double lp[3], lm[3];
-    for (int d = 0; d < 3; ++d) {
-      lp[d] = bh_loc(iv[d] + (d == d0), dx, p.domlen[d]);
-      lm[d] = bh_loc(iv[d] - (d == d0), dx, p.domlen[d]);
-    }
-    const double dphidx = 0.5 / dx * (+bh_phi(p, lp[0], lp[1], lp[2]) - bh_phi(p, lm[0], lm[1], lm[2]));
-    rho_grad = rho_grad + 0.5 * dphidx * dphidx;
-  }
   double l1[3] = {loc[0] - p.off1, loc[1], loc[2]}, l2[3] = {loc[0] - p.off2, loc[1], loc[2]};
   const double r1 = sqrt(l1[0] * l1[0] + l1[1] * l1[1] + l1[2] * l1[2]);
   const double r2 = sqrt(l2[0] * l2[0] + l2[1] * l2[1] + l2[2] * l2[2]);
@@ -932,21 +914,95 @@ __global__ __launch_bounds__(256) void k_binary_bh(double *__restrict__ acoef,
   const double n2[3] = {l2[0] / r2, l2[1] / r2, l2[2] / r2};
   const double J1[3] = {0.0, 0.0, p.spin1}, J2[3] = {0.0, 0.0, p.spin2};
   const double P1[3] = {0.0, p.mom1, 0.0}, P2[3] = {0.0, p.mom2, 0.0};
-  const double A11 = bh_Aij(0, 0, r1, r2, n1, n2, J1, J2, P1, P2);
-  const double A22 = bh_Aij(1, 1, r1, r2, n1, n2, J1, J2, P1, P2);
-  const double A33 = bh_Aij(2, 2, r1, r2, n1, n2, J1, J2, P1, P2);
-  const double A12 = bh_Aij(0, 1, r1, r2, n1, n2, J1, J2, P1, P2);
-  const double A13 = bh_Aij(0, 2, r1, r2, n1, n2, J1, J2, P1, P2);
-  const double A23 = bh_Aij(1, 2, r1, r2, n1, n2, J1, J2, P1, P2);
-  const double A2 = pow(A11, 2.0) + pow(A22, 2.0) + pow(A33, 2.0) + 2 * pow(A12, 2.0) +
-                    2 * pow(A13, 2.0) + 2 * pow(A23, 2.0);  // SetLevelData.cpp:312-317
+  BhBowenYork c;
+  c.A11 = bh_Aij(0, 0, r1, r2, n1, n2, J1, J2, P1, P2);  // SetBinaryBH.H:77-82
+  c.A22 = bh_Aij(1, 1, r1, r2, n1, n2, J1, J2, P1, P2);
+  c.A33 = bh_Aij(2, 2, r1, r2, n1, n2, J1, J2, P1, P2);
+  c.A12 = bh_Aij(0, 1, r1, r2, n1, n2, J1, J2, P1, P2);
+  c.A13 = bh_Aij(0, 2, r1, r2, n1, n2, J1, J2, P1, P2);
+  c.A23 = bh_Aij(1, 2, r1, r2, n1, n2, J1, J2, P1, P2);
+  c.psi_bh = p.m1 / r1 + p.m2 / r2;  // SetBinaryBH.H:85-99
+  return c;
+}
+// A2 = A_ij A^ij (SetLevelData.cpp:312-317, and :223-228 for the regrid condition)
+__device__ __forceinline__ double bh_A2(const BhBowenYork &c) {
+  return pow(c.A11, 2.0) + pow(c.A22, 2.0) + pow(c.A33, 2.0) + 2 * pow(c.A12, 2.0) +
+         2 * pow(c.A13, 2.0) + 2 * pow(c.A23, 2.0);
+}
+
+// GETRHOGRADPHIF (SetLevelDataF.ChF:65-103) of a stored field at one cell,
+// the field's ghost layer read as is
+__device__ __forceinline__ double phi_rho_grad(const double *__restrict__ phi, long idx,
+                                               const BoxArgs &g, double dx) {
+  const long st[3] = {1, g.sy, g.sz};
+  double acc = 0.0;
+  for (int d0 = 0; d0 < 3; ++d0) {
+    const double dphidx = 0.5 / dx * (+phi[idx + st[d0]] - phi[idx - st[d0]]);
+    acc = acc + 0.5 * dphidx * dphidx;
+  }
+  return acc;
+}
+
+// where a generator takes phi_0 from, chosen at compile time.  STORED: the
+// field `phi` (one value per cell of the box grown by one, see k_fill_phi);
+// else MyPhiFunction.H's Gaussian evaluated in place, `phi` unused.
+template <bool STORED>
+__device__ __forceinline__ double bh_phi0(const BhParams &p, const double *__restrict__ phi,
+                                          const int iv[3], long idx, double dx) {
+  if constexpr (STORED) {
+    return phi[idx];
+  } else {
+    return bh_phi(p, bh_loc(iv[0], dx, p.domlen[0]), bh_loc(iv[1], dx, p.domlen[1]),
+                  bh_loc(iv[2], dx, p.domlen[2]));
+  }
+}
+// rho_grad of phi_0: GETRHOGRADPHIF, SetLevelDataF.ChF:65-103
+template <bool STORED>
+__device__ __forceinline__ double bh_rho_grad(const BhParams &p, const double *__restrict__ phi,
+                                              const int iv[3], long idx, const BoxArgs &g,
+                                              double dx) {
+  if constexpr (STORED) {
+    return phi_rho_grad(phi, idx, g, dx);
+  } else {
+    double rho_grad = 0.0;
+    for (int d0 = 0; d0 < 3; ++d0) {
+      double lp[3], lm[3];
+      for (int d = 0; d < 3; ++d) {
+        lp[d] = bh_loc(iv[d] + (d == d0), dx, p.domlen[d]);
+        lm[d] = bh_loc(iv[d] - (d == d0), dx, p.domlen[d]);
+      }
+      const double dphidx = 0.5 / dx * (+bh_phi(p, lp[0], lp[1], lp[2]) - bh_phi(p, lm[0], lm[1], lm[2]));
+      rho_grad = rho_grad + 0.5 * dphidx * dphidx;
+    }
+    return rho_grad;
+  }
+}
+
+// set_a_coef + set_rhs (SetLevelData.cpp:73-127, :281-325); psi == nullptr:
+// psi = 1 everywhere (NL iteration 0), else psi read with its ghost layer
+// INTEGRAND: set_constant_K_integrand (SetLevelData.cpp:131-180) into acoef
+// instead (m taken at K = 0, rhs untouched)
+// STORED: phi_0 read from `phi` with its ghost layer (see bh_phi0)
+template <bool INTEGRAND, bool STORED>
+__global__ __launch_bounds__(256) void k_binary_bh(double *__restrict__ acoef,
+                                                   double *__restrict__ rhs,
+                                                   const double *__restrict__ psi,
+                                                   const double *__restrict__ phi,
+                                                   const BoxArgs g, double dx, const BhParams p) {
+  const int i = blockIdx.x * TX + threadIdx.x;
+  const int j = blockIdx.y * TY + threadIdx.y;
+  const int k = blockIdx.z;
+  if (i >= g.nx || j >= g.ny) return;
+  const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k};
+  const long idx = (long)i + (long)j * g.sy + (long)k * g.sz;
+  const double rho_grad = bh_rho_grad<STORED>(p, phi, iv, idx, g, dx);
+  const BhBowenYork c = bh_bowen_york(p, iv, dx);
+  const double A2 = bh_A2(c);
   const double rho = 0.5 * 0.0 * 0.0 + 0.0;
   const double K = INTEGRAND ? 0.0 : p.constant_K;  // set_m_value(.., 0.0) for the integrand
   const double m = (2.0 / 3.0) * (K * K) - 16.0 * M_PI * p.G_Newton * rho;
-  const double psi_bh = p.m1 / r1 + p.m2 / r2;  // SetBinaryBH.H:85-99
-  const long idx = (long)i + (long)j * g.sy + (long)k * g.sz;
   const double psi_c = psi ? psi[idx] : 1.0;
-  const double psi_0 = psi_c + psi_bh;  // SetLevelData.cpp:319-320
+  const double psi_0 = psi_c + c.psi_bh;  // SetLevelData.cpp:319-320
   double lap = 0.0;  // GETLAPLACIANPSIF, SetLevelDataF.ChF:15-58 (2nd order)
   const long st[3] = {1, g.sy, g.sz};
   for (int d0 = 0; d0 < 3; ++d0) {
@@ -965,52 +1021,15 @@ __global__ __launch_bounds__(256) void k_binary_bh(double *__restrict__ acoef,
              2.0 * M_PI * p.G_Newton * rho_grad * psi_0 - lap;  // SetLevelData.cpp:121-124
 }
 
-// The psi-independent terms of one cell, in the expression order of
-// k_binary_bh (which keeps its own copy, so that its code does not move):
-// rho_grad (GETRHOGRADPHIF of phi_0, SetLevelDataF.ChF:65-103), A2 = A_ij A^ij
-// (SetBinaryBH.H:24-82, SetLevelData.cpp:223-228) and psi_bh (SetBinaryBH.H:85-99)
-struct BhCell {
-  double rho_grad, A2, psi_bh;
-};
-__device__ BhCell bh_cell(const BhParams &p, const int iv[3], double dx) {
-  double loc[3];
-  for (int d = 0; d < 3; ++d) loc[d] = bh_loc(iv[d], dx, p.domlen[d]);
-  BhCell c;
-  c.rho_grad = 0.0;
-  for (int d0 = 0; d0 < 3; ++d0) {
-    double lp[3], lm[3];
-    for (int d = 0; d < 3; ++d) {
-      lp[d] = bh_loc(iv[d] + (d == d0), dx, p.domlen[d]);
-      lm[d] = bh_loc(iv[d] - (d == d0), dx, p.domlen[d]);
-    }
-    const double dphidx = 0.5 / dx * (+bh_phi(p, lp[0], lp[1], lp[2]) - bh_phi(p, lm[0], lm[1], lm[2]));
-    c.rho_grad = c.rho_grad + 0.5 * dphidx * dphidx;
-  }
-  double l1[3] = {loc[0] - p.off1, loc[1], loc[2]}, l2[3] = {loc[0] - p.off2, loc[1], loc[2]};
-  const double r1 = sqrt(l1[0] * l1[0] + l1[1] * l1[1] + l1[2] * l1[2]);
-  const double r2 = sqrt(l2[0] * l2[0] + l2[1] * l2[1] + l2[2] * l2[2]);
-  const double n1[3] = {l1[0] / r1, l1[1] / r1, l1[2] / r1};
-  const double n2[3] = {l2[0] / r2, l2[1] / r2, l2[2] / r2};
-  const double J1[3] = {0.0, 0.0, p.spin1}, J2[3] = {0.0, 0.0, p.spin2};
-  const double P1[3] = {0.0, p.mom1, 0.0}, P2[3] = {0.0, p.mom2, 0.0};
-  const double A11 = bh_Aij(0, 0, r1, r2, n1, n2, J1, J2, P1, P2);
-  const double A22 = bh_Aij(1, 1, r1, r2, n1, n2, J1, J2, P1, P2);
-  const double A33 = bh_Aij(2, 2, r1, r2, n1, n2, J1, J2, P1, P2);
-  const double A12 = bh_Aij(0, 1, r1, r2, n1, n2, J1, J2, P1, P2);
-  const double A13 = bh_Aij(0, 2, r1, r2, n1, n2, J1, J2, P1, P2);
-  const double A23 = bh_Aij(1, 2, r1, r2, n1, n2, J1, J2, P1, P2);
-  c.A2 = pow(A11, 2.0) + pow(A22, 2.0) + pow(A33, 2.0) + 2 * pow(A12, 2.0) + 2 * pow(A13, 2.0) +
-         2 * pow(A23, 2.0);
-  c.psi_bh = p.m1 / r1 + p.m2 / r2;
-  return c;
-}
-
 // set_regrid_condition (SetLevelData.cpp:190-240): the field whose magnitude
 // drives set_grids' tagging.  m is set_m_value(.., K = 0); A2, rho_grad and
 // psi_0 as in k_binary_bh; psi == nullptr: psi = 1 (set_grids evaluates it
 // right after set_initial_conditions).  No ghost cell of psi is read.
+// STORED: phi_0 read from `phi` with its ghost layer (see bh_phi0)
+template <bool STORED>
 __global__ __launch_bounds__(256) void k_regrid_condition(double *__restrict__ out,
                                                           const double *__restrict__ psi,
+                                                          const double *__restrict__ phi,
                                                           const BoxArgs g, double dx,
                                                           const BhParams p) {
   const int i = blockIdx.x * TX + threadIdx.x;
@@ -1018,13 +1037,15 @@ __global__ __launch_bounds__(256) void k_regrid_condition(double *__restrict__ o
   const int k = blockIdx.z;
   if (i >= g.nx || j >= g.ny) return;
   const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k};
-  const BhCell c = bh_cell(p, iv, dx);
+  const long idx = (long)i + (long)j * g.sy + (long)k * g.sz;
+  const double rho_grad = bh_rho_grad<STORED>(p, phi, iv, idx, g, dx);
+  const BhBowenYork c = bh_bowen_york(p, iv, dx);
+  const double A2 = bh_A2(c);
   const double rho = 0.5 * 0.0 * 0.0 + 0.0;
   const double m = (2.0 / 3.0) * (0.0 * 0.0) - 16.0 * M_PI * p.G_Newton * rho;  // K = 0 (:219)
-  const long idx = (long)i + (long)j * g.sy + (long)k * g.sz;
   const double psi_0 = (psi ? psi[idx] : 1.0) + c.psi_bh;  // :232-233
-  out[idx] = 1.5 * fabs(m) + 1.5 * c.A2 * pow(psi_0, -7.0) +
-             24.0 * M_PI * p.G_Newton * fabs(c.rho_grad) * pow(psi_0, 1.0) + log(psi_0);  // :234-237
+  out[idx] = 1.5 * fabs(m) + 1.5 * A2 * pow(psi_0, -7.0) +
+             24.0 * M_PI * p.G_Newton * fabs(rho_grad) * pow(psi_0, 1.0) + log(psi_0);  // :234-237
 }
 
 // set_tag_cells (SetGrids.cpp:172-207) onto the clustering lattice: a cell of
@@ -1103,13 +1124,7 @@ __global__ __launch_bounds__(256) void k_rho_grad_phi(double *__restrict__ r,
   const int k = blockIdx.z;
   if (i >= g.nx || j >= g.ny) return;
   const long idx = (long)i + (long)j * g.sy + (long)k * g.sz;
-  const long st[3] = {1, g.sy, g.sz};
-  double acc = 0.0;
-  for (int d0 = 0; d0 < 3; ++d0) {
-    const double dphidx = 0.5 / dx * (+phi[idx + st[d0]] - phi[idx - st[d0]]);
-    acc = acc + 0.5 * dphidx * dphidx;
-  }
-  r[idx] = acc;
+  r[idx] = phi_rho_grad(phi, idx, g, dx);
 }
 
 // ---- output: the components WriteOutput.H writes, for
@@ -1120,11 +1135,13 @@ __global__ __launch_bounds__(256) void k_rho_grad_phi(double *__restrict__ r,
 // KIND 1: output_solver_data's tempData (WriteOutput.H:84-100): dpsi, rhs and
 //         the 8 multigrid_vars (psi, A11_0 .. A33_0, phi_0; the A_ij_0 and
 //         phi_0 of set_initial_conditions, SetLevelData.cpp:31-72)
-template <int KIND>
+// STORED: phi (KIND 0, v[25]) / phi_0 (KIND 1) copied from `phi` (see bh_phi0)
+template <int KIND, bool STORED>
 __global__ __launch_bounds__(256) void k_output_vars(double *__restrict__ out,
                                                      const double *__restrict__ psi,
                                                      const double *__restrict__ dpsi,
                                                      const double *__restrict__ rhs,
+                                                     const double *__restrict__ phi,
                                                      const BoxArgs g, int k0, int nk, double dx,
                                                      const BhParams p) {
   const int i = blockIdx.x * TX + threadIdx.x;
@@ -1132,34 +1149,20 @@ __global__ __launch_bounds__(256) void k_output_vars(double *__restrict__ out,
   const int k = blockIdx.z;
   if (i >= g.nx || j >= g.ny) return;
   const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k0 + k};
-  double loc[3];
-  for (int d = 0; d < 3; ++d) loc[d] = bh_loc(iv[d], dx, p.domlen[d]);
-  double l1[3] = {loc[0] - p.off1, loc[1], loc[2]}, l2[3] = {loc[0] - p.off2, loc[1], loc[2]};
-  const double r1 = sqrt(l1[0] * l1[0] + l1[1] * l1[1] + l1[2] * l1[2]);
-  const double r2 = sqrt(l2[0] * l2[0] + l2[1] * l2[1] + l2[2] * l2[2]);
-  const double n1[3] = {l1[0] / r1, l1[1] / r1, l1[2] / r1};
-  const double n2[3] = {l2[0] / r2, l2[1] / r2, l2[2] / r2};
-  const double J1[3] = {0.0, 0.0, p.spin1}, J2[3] = {0.0, 0.0, p.spin2};
-  const double P1[3] = {0.0, p.mom1, 0.0}, P2[3] = {0.0, p.mom2, 0.0};
-  const double A11 = bh_Aij(0, 0, r1, r2, n1, n2, J1, J2, P1, P2);  // SetBinaryBH.H:77-82
-  const double A22 = bh_Aij(1, 1, r1, r2, n1, n2, J1, J2, P1, P2);
-  const double A33 = bh_Aij(2, 2, r1, r2, n1, n2, J1, J2, P1, P2);
-  const double A12 = bh_Aij(0, 1, r1, r2, n1, n2, J1, J2, P1, P2);
-  const double A13 = bh_Aij(0, 2, r1, r2, n1, n2, J1, J2, P1, P2);
-  const double A23 = bh_Aij(1, 2, r1, r2, n1, n2, J1, J2, P1, P2);
-  const double phi0 = bh_phi(p, loc[0], loc[1], loc[2]);  // MyPhiFunction.H
+  const BhBowenYork b = bh_bowen_york(p, iv, dx);
   const long idx = (long)i + (long)j * g.sy + (long)(k0 + k) * g.sz;
+  const double phi0 = bh_phi0<STORED>(p, phi, iv, idx, dx);  // MyPhiFunction.H
   const double psi_c = psi[idx];
   const long V = (long)g.nx * g.ny * nk;
   double *o = out + (long)i + (long)g.nx * (j + (long)g.ny * k);
   if (KIND == 1) {
-    const double v[10] = {dpsi[idx], rhs[idx], psi_c, A11, A12, A13, A22, A23, A33, phi0};
+    const double v[10] = {dpsi[idx], rhs[idx], psi_c, b.A11, b.A12, b.A13, b.A22, b.A23, b.A33,
+                          phi0};
 #pragma unroll
     for (int c = 0; c < 10; ++c) o[c * V] = v[c];
     return;
   }
-  const double psi_bh = p.m1 / r1 + p.m2 / r2;      // SetBinaryBH.H:85-99
-  const double chi = pow(psi_c + psi_bh, -4.0);      // SetLevelData.cpp:381-383
+  const double chi = pow(psi_c + b.psi_bh, -4.0);    // SetLevelData.cpp:381-383
   const double factor = pow(chi, 1.5);               // :384
   double v[31];
 #pragma unroll
@@ -1169,12 +1172,12 @@ __global__ __launch_bounds__(256) void k_output_vars(double *__restrict__ out,
   v[7] = p.constant_K;                               // K (:371)
   v[0] = chi;
   v[25] = phi0;                                      // phi (:387)
-  v[8] = A11 * factor;                               // A11 .. A33 (:388-393)
-  v[9] = A12 * factor;
-  v[10] = A13 * factor;
-  v[11] = A22 * factor;
-  v[12] = A23 * factor;
-  v[13] = A33 * factor;
+  v[8] = b.A11 * factor;                             // A11 .. A33 (:388-393)
+  v[9] = b.A12 * factor;
+  v[10] = b.A13 * factor;
+  v[11] = b.A22 * factor;
+  v[12] = b.A23 * factor;
+  v[13] = b.A33 * factor;
 #pragma unroll
   for (int c = 0; c < 31; ++c) o[c * V] = v[c];
 }
@@ -1183,9 +1186,8 @@ __global__ __launch_bounds__(256) void k_output_vars(double *__restrict__ out,
 // fills, SetLevelData.cpp:32-71): one value per cell of the box grown by one,
 // the profile at that cell's centre (ghost cells outside the domain or under
 // a coarse-fine boundary included; never exchanged, BC-filled or
-// interpolated).  The generators below are the analytic ones above with
-// every bh_phi evaluation replaced by a load of the stored field; the
-// analytic kernels keep their own code, so that it does not move.
+// interpolated).  The STORED instantiations of the generators above load it
+// wherever the analytic ones evaluate bh_phi.
 //
 // PROFILE is a template parameter (no runtime switch in the kernel):
 // kPhiGaussian is bh_phi itself, kPhiSine the profile MyPhiFunction.H names
@@ -1210,157 +1212,6 @@ __global__ __launch_bounds__(256) void k_fill_phi(double *__restrict__ phi, cons
   const double y = bh_loc(g.glo[1] + j, dx, p.domlen[1]);
   const double z = bh_loc(g.glo[2] + k, dx, p.domlen[2]);
   phi[(long)i + (long)j * g.sy + (long)k * g.sz] = phi_profile<PROFILE>(p, x, y, z);
-}
-
-// GETRHOGRADPHIF of the stored field at one cell, in k_rho_grad_phi's order
-__device__ __forceinline__ double phi_rho_grad(const double *__restrict__ phi, long idx,
-                                               const BoxArgs &g, double dx) {
-  const long st[3] = {1, g.sy, g.sz};
-  double acc = 0.0;
-  for (int d0 = 0; d0 < 3; ++d0) {
-    const double dphidx = 0.5 / dx * (+phi[idx + st[d0]] - phi[idx - st[d0]]);
-    acc = acc + 0.5 * dphidx * dphidx;
-  }
-  return acc;
-}
-
-// the Bowen-York terms of one cell in the analytic kernels' expression order:
-// A_ij_0 (SetBinaryBH.H:24-82) and psi_bh (:85-99)
-struct BhBowenYork {
-  double A11, A12, A13, A22, A23, A33, psi_bh;
-};
-__device__ BhBowenYork bh_bowen_york(const BhParams &p, const int iv[3], double dx) {
-  double loc[3];
-  for (int d = 0; d < 3; ++d) loc[d] = bh_loc(iv[d], dx, p.domlen[d]);
-  double l1[3] = {loc[0] - p.off1, loc[1], loc[2]}, l2[3] = {loc[0] - p.off2, loc[1], loc[2]};
-  const double r1 = sqrt(l1[0] * l1[0] + l1[1] * l1[1] + l1[2] * l1[2]);
-  const double r2 = sqrt(l2[0] * l2[0] + l2[1] * l2[1] + l2[2] * l2[2]);
-  const double n1[3] = {l1[0] / r1, l1[1] / r1, l1[2] / r1};
-  const double n2[3] = {l2[0] / r2, l2[1] / r2, l2[2] / r2};
-  const double J1[3] = {0.0, 0.0, p.spin1}, J2[3] = {0.0, 0.0, p.spin2};
-  const double P1[3] = {0.0, p.mom1, 0.0}, P2[3] = {0.0, p.mom2, 0.0};
-  BhBowenYork c;
-  c.A11 = bh_Aij(0, 0, r1, r2, n1, n2, J1, J2, P1, P2);
-  c.A22 = bh_Aij(1, 1, r1, r2, n1, n2, J1, J2, P1, P2);
-  c.A33 = bh_Aij(2, 2, r1, r2, n1, n2, J1, J2, P1, P2);
-  c.A12 = bh_Aij(0, 1, r1, r2, n1, n2, J1, J2, P1, P2);
-  c.A13 = bh_Aij(0, 2, r1, r2, n1, n2, J1, J2, P1, P2);
-  c.A23 = bh_Aij(1, 2, r1, r2, n1, n2, J1, J2, P1, P2);
-  c.psi_bh = p.m1 / r1 + p.m2 / r2;
-  return c;
-}
-__device__ __forceinline__ double bh_A2(const BhBowenYork &c) {  // SetLevelData.cpp:312-317
-  return pow(c.A11, 2.0) + pow(c.A22, 2.0) + pow(c.A33, 2.0) + 2 * pow(c.A12, 2.0) +
-         2 * pow(c.A13, 2.0) + 2 * pow(c.A23, 2.0);
-}
-
-// k_binary_bh with phi_0 read from `phi` (with its ghost layer)
-template <bool INTEGRAND>
-__global__ __launch_bounds__(256) void k_binary_bh_phi(double *__restrict__ acoef,
-                                                       double *__restrict__ rhs,
-                                                       const double *__restrict__ psi,
-                                                       const double *__restrict__ phi,
-                                                       const BoxArgs g, double dx,
-                                                       const BhParams p) {
-  const int i = blockIdx.x * TX + threadIdx.x;
-  const int j = blockIdx.y * TY + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i >= g.nx || j >= g.ny) return;
-  const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k};
-  const long idx = (long)i + (long)j * g.sy + (long)k * g.sz;
-  const double rho_grad = phi_rho_grad(phi, idx, g, dx);
-  const BhBowenYork c = bh_bowen_york(p, iv, dx);
-  const double A2 = bh_A2(c);
-  const double rho = 0.5 * 0.0 * 0.0 + 0.0;
-  const double K = INTEGRAND ? 0.0 : p.constant_K;
-  const double m = (2.0 / 3.0) * (K * K) - 16.0 * M_PI * p.G_Newton * rho;
-  const double psi_c = psi ? psi[idx] : 1.0;
-  const double psi_0 = psi_c + c.psi_bh;
-  double lap = 0.0;
-  const long st[3] = {1, g.sy, g.sz};
-  for (int d0 = 0; d0 < 3; ++d0) {
-    const double pm = psi ? psi[idx - st[d0]] : 1.0, pp = psi ? psi[idx + st[d0]] : 1.0;
-    lap = lap + 1.0 / dx / dx * (+1.0 * pm - 2.0 * psi_c + 1.0 * pp);
-  }
-  if (INTEGRAND) {
-    acoef[idx] = -1.5 * m + 1.5 * A2 * pow(psi_0, -12.0) +
-                 24.0 * M_PI * p.G_Newton * rho_grad * pow(psi_0, -4.0) +
-                 12.0 * lap * pow(psi_0, -5.0);
-    return;
-  }
-  acoef[idx] = -0.625 * m * pow(psi_0, 4.0) - A2 * pow(psi_0, -8.0) +
-               2.0 * M_PI * p.G_Newton * rho_grad;
-  rhs[idx] = 0.125 * m * pow(psi_0, 5.0) - 0.125 * A2 * pow(psi_0, -7.0) -
-             2.0 * M_PI * p.G_Newton * rho_grad * psi_0 - lap;
-}
-
-// k_regrid_condition with phi_0 read from `phi`
-__global__ __launch_bounds__(256) void k_regrid_condition_phi(double *__restrict__ out,
-                                                              const double *__restrict__ psi,
-                                                              const double *__restrict__ phi,
-                                                              const BoxArgs g, double dx,
-                                                              const BhParams p) {
-  const int i = blockIdx.x * TX + threadIdx.x;
-  const int j = blockIdx.y * TY + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i >= g.nx || j >= g.ny) return;
-  const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k};
-  const long idx = (long)i + (long)j * g.sy + (long)k * g.sz;
-  const double rho_grad = phi_rho_grad(phi, idx, g, dx);
-  const BhBowenYork c = bh_bowen_york(p, iv, dx);
-  const double A2 = bh_A2(c);
-  const double rho = 0.5 * 0.0 * 0.0 + 0.0;
-  const double m = (2.0 / 3.0) * (0.0 * 0.0) - 16.0 * M_PI * p.G_Newton * rho;
-  const double psi_0 = (psi ? psi[idx] : 1.0) + c.psi_bh;
-  out[idx] = 1.5 * fabs(m) + 1.5 * A2 * pow(psi_0, -7.0) +
-             24.0 * M_PI * p.G_Newton * fabs(rho_grad) * pow(psi_0, 1.0) + log(psi_0);
-}
-
-// k_output_vars with phi (KIND 0, v[25]) / phi_0 (KIND 1) copied from `phi`
-template <int KIND>
-__global__ __launch_bounds__(256) void k_output_vars_phi(double *__restrict__ out,
-                                                         const double *__restrict__ psi,
-                                                         const double *__restrict__ dpsi,
-                                                         const double *__restrict__ rhs,
-                                                         const double *__restrict__ phi,
-                                                         const BoxArgs g, int k0, int nk,
-                                                         double dx, const BhParams p) {
-  const int i = blockIdx.x * TX + threadIdx.x;
-  const int j = blockIdx.y * TY + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i >= g.nx || j >= g.ny) return;
-  const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k0 + k};
-  const BhBowenYork b = bh_bowen_york(p, iv, dx);
-  const long idx = (long)i + (long)j * g.sy + (long)(k0 + k) * g.sz;
-  const double phi0 = phi[idx];
-  const double psi_c = psi[idx];
-  const long V = (long)g.nx * g.ny * nk;
-  double *o = out + (long)i + (long)g.nx * (j + (long)g.ny * k);
-  if (KIND == 1) {
-    const double v[10] = {dpsi[idx], rhs[idx], psi_c, b.A11, b.A12, b.A13, b.A22, b.A23, b.A33,
-                          phi0};
-#pragma unroll
-    for (int c = 0; c < 10; ++c) o[c * V] = v[c];
-    return;
-  }
-  const double chi = pow(psi_c + b.psi_bh, -4.0);
-  const double factor = pow(chi, 1.5);
-  double v[31];
-#pragma unroll
-  for (int c = 0; c < 31; ++c) v[c] = 0.0;
-  v[1] = v[4] = v[6] = 1.0;
-  v[18] = 1.0;
-  v[7] = p.constant_K;
-  v[0] = chi;
-  v[25] = phi0;
-  v[8] = b.A11 * factor;
-  v[9] = b.A12 * factor;
-  v[10] = b.A13 * factor;
-  v[11] = b.A22 * factor;
-  v[12] = b.A23 * factor;
-  v[13] = b.A33 * factor;
-#pragma unroll
-  for (int c = 0; c < 31; ++c) o[c * V] = v[c];
 }
 
 inline dim3 grid_cells(int nx, int ny, int nz) {
@@ -2204,24 +2055,36 @@ void copy_items(const CopyItem *d_items, int nitems, long max_cells, double *con
   check_launch();
 }
 
-void binary_bh_coefs(double *acoef, double *rhs, const double *psi, const BoxArgs &g, double dx,
-                     const BhParams &p, hipStream_t st) {
+template <bool INTEGRAND>
+static void launch_binary_bh(double *acoef, double *rhs, const double *psi, const double *phi,
+                             const BoxArgs &g, double dx, const BhParams &p, hipStream_t st) {
   if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
-  k_binary_bh<false><<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(acoef, rhs, psi, g, dx, p);
+  const dim3 grid = grid_cells(g.nx, g.ny, g.nz);
+  if (phi)
+    k_binary_bh<INTEGRAND, true><<<grid, kBlock, 0, st>>>(acoef, rhs, psi, phi, g, dx, p);
+  else
+    k_binary_bh<INTEGRAND, false><<<grid, kBlock, 0, st>>>(acoef, rhs, psi, nullptr, g, dx, p);
   check_launch();
 }
 
-void constant_k_integrand(double *out, const double *psi, const BoxArgs &g, double dx,
-                          const BhParams &p, hipStream_t st) {
-  if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
-  k_binary_bh<true><<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(out, nullptr, psi, g, dx, p);
-  check_launch();
+void binary_bh_coefs(double *acoef, double *rhs, const double *psi, const double *phi,
+                     const BoxArgs &g, double dx, const BhParams &p, hipStream_t st) {
+  launch_binary_bh<false>(acoef, rhs, psi, phi, g, dx, p, st);
 }
 
-void regrid_condition(double *out, const double *psi, const BoxArgs &g, double dx,
-                      const BhParams &p, hipStream_t st) {
+void constant_k_integrand(double *out, const double *psi, const double *phi, const BoxArgs &g,
+                          double dx, const BhParams &p, hipStream_t st) {
+  launch_binary_bh<true>(out, nullptr, psi, phi, g, dx, p, st);
+}
+
+void regrid_condition(double *out, const double *psi, const double *phi, const BoxArgs &g,
+                      double dx, const BhParams &p, hipStream_t st) {
   if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
-  k_regrid_condition<<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(out, psi, g, dx, p);
+  const dim3 grid = grid_cells(g.nx, g.ny, g.nz);
+  if (phi)
+    k_regrid_condition<true><<<grid, kBlock, 0, st>>>(out, psi, phi, g, dx, p);
+  else
+    k_regrid_condition<false><<<grid, kBlock, 0, st>>>(out, psi, nullptr, g, dx, p);
   check_launch();
 }
 
@@ -2254,15 +2117,26 @@ void rho_grad_phi(double *r, const double *phi, const BoxArgs &g, double dx, hip
   check_launch();
 }
 
+template <int KIND>
+static void launch_output_vars(double *out, const double *psi, const double *dpsi,
+                               const double *rhs, const double *phi, const BoxArgs &g, int k0,
+                               int nk, double dx, const BhParams &p, hipStream_t st) {
+  const dim3 grid = grid_cells(g.nx, g.ny, nk);
+  if (phi)
+    k_output_vars<KIND, true><<<grid, kBlock, 0, st>>>(out, psi, dpsi, rhs, phi, g, k0, nk, dx, p);
+  else
+    k_output_vars<KIND, false><<<grid, kBlock, 0, st>>>(out, psi, dpsi, rhs, nullptr, g, k0, nk,
+                                                        dx, p);
+}
+
 void output_vars(int kind, double *out, const double *psi, const double *dpsi, const double *rhs,
-                 const BoxArgs &g, int k0, int nk, double dx, const BhParams &p, hipStream_t st) {
+                 const double *phi, const BoxArgs &g, int k0, int nk, double dx, const BhParams &p,
+                 hipStream_t st) {
   if (g.nx <= 0 || g.ny <= 0 || nk <= 0) return;
   if (kind == 0)
-    k_output_vars<0><<<grid_cells(g.nx, g.ny, nk), kBlock, 0, st>>>(out, psi, dpsi, rhs, g, k0, nk,
-                                                                    dx, p);
+    launch_output_vars<0>(out, psi, dpsi, rhs, phi, g, k0, nk, dx, p, st);
   else
-    k_output_vars<1><<<grid_cells(g.nx, g.ny, nk), kBlock, 0, st>>>(out, psi, dpsi, rhs, g, k0, nk,
-                                                                    dx, p);
+    launch_output_vars<1>(out, psi, dpsi, rhs, phi, g, k0, nk, dx, p, st);
   check_launch();
 }
 
@@ -2276,42 +2150,6 @@ void fill_phi(int profile, double *phi, const BoxArgs &g, double dx, const BhPar
     k_fill_phi<kPhiGaussian><<<grid, kBlock, 0, st>>>(phi, g, dx, p);
   else
     k_fill_phi<kPhiSine><<<grid, kBlock, 0, st>>>(phi, g, dx, p);
-  check_launch();
-}
-
-void binary_bh_coefs_phi(double *acoef, double *rhs, const double *psi, const double *phi,
-                         const BoxArgs &g, double dx, const BhParams &p, hipStream_t st) {
-  if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
-  k_binary_bh_phi<false><<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(acoef, rhs, psi, phi, g,
-                                                                           dx, p);
-  check_launch();
-}
-
-void constant_k_integrand_phi(double *out, const double *psi, const double *phi, const BoxArgs &g,
-                              double dx, const BhParams &p, hipStream_t st) {
-  if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
-  k_binary_bh_phi<true><<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(out, nullptr, psi, phi, g,
-                                                                          dx, p);
-  check_launch();
-}
-
-void regrid_condition_phi(double *out, const double *psi, const double *phi, const BoxArgs &g,
-                          double dx, const BhParams &p, hipStream_t st) {
-  if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
-  k_regrid_condition_phi<<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(out, psi, phi, g, dx, p);
-  check_launch();
-}
-
-void output_vars_phi(int kind, double *out, const double *psi, const double *dpsi,
-                     const double *rhs, const double *phi, const BoxArgs &g, int k0, int nk,
-                     double dx, const BhParams &p, hipStream_t st) {
-  if (g.nx <= 0 || g.ny <= 0 || nk <= 0) return;
-  if (kind == 0)
-    k_output_vars_phi<0><<<grid_cells(g.nx, g.ny, nk), kBlock, 0, st>>>(out, psi, dpsi, rhs, phi, g,
-                                                                        k0, nk, dx, p);
-  else
-    k_output_vars_phi<1><<<grid_cells(g.nx, g.ny, nk), kBlock, 0, st>>>(out, psi, dpsi, rhs, phi, g,
-                                                                        k0, nk, dx, p);
   check_launch();
 }
 

@@ -202,14 +202,17 @@ struct BhParams {
   double m1, m2, spin1, spin2, off1, off2, mom1, mom2, constant_K;
 };
 // psi: nullptr = psi 1 everywhere, else read with its ghost layer
-void binary_bh_coefs(double *acoef, double *rhs, const double *psi, const BoxArgs &g, double dx,
-                     const BhParams &p, hipStream_t st);
+// phi (here and in the generators below): nullptr = phi_0 is MyPhiFunction.H's
+// Gaussian evaluated in place, else the stored phi_0 (see fill_phi), read with
+// its one ghost layer next to each face
+void binary_bh_coefs(double *acoef, double *rhs, const double *psi, const double *phi,
+                     const BoxArgs &g, double dx, const BhParams &p, hipStream_t st);
 // set_constant_K_integrand (SetLevelData.cpp:131-180) at psi (nullptr: 1)
-void constant_k_integrand(double *out, const double *psi, const BoxArgs &g, double dx,
-                          const BhParams &p, hipStream_t st);
+void constant_k_integrand(double *out, const double *psi, const double *phi, const BoxArgs &g,
+                          double dx, const BhParams &p, hipStream_t st);
 // set_regrid_condition (SetLevelData.cpp:190-240) at psi (nullptr: 1)
-void regrid_condition(double *out, const double *psi, const BoxArgs &g, double dx,
-                      const BhParams &p, hipStream_t st);
+void regrid_condition(double *out, const double *psi, const double *phi, const BoxArgs &g,
+                      double dx, const BhParams &p, hipStream_t st);
 // set_tag_cells (SetGrids.cpp:172-207) of one box onto a byte mask over lattice
 // cells [lat_lo, lat_lo + lat_n) (lattice index = floor(cell / c), x fastest):
 // cells with |cond| >= tag_val, grown by `grow` and clipped to [dom_lo,
@@ -226,23 +229,13 @@ void rho_grad_phi(double *r, const double *phi, const BoxArgs &g, double dx, hip
 // phi_0
 constexpr int kNumGRChomboVars = 31, kNumSolverVars = 10;
 void output_vars(int kind, double *out, const double *psi, const double *dpsi, const double *rhs,
-                 const BoxArgs &g, int k0, int nk, double dx, const BhParams &p, hipStream_t st);
+                 const double *phi, const BoxArgs &g, int k0, int nk, double dx, const BhParams &p,
+                 hipStream_t st);
 // ---- phi_0 as a stored field (SetLevelData.cpp:32-71's c_phi_0): the profile
-// at every cell centre of the box grown by one; the generators above with
-// phi_0 loaded from `phi` (read with its one ghost layer next to each face)
-// instead of evaluated
+// at every cell centre of the box grown by one, for the generators' `phi`
 enum PhiProfile { kPhiGaussian = 0, kPhiSine = 1 };  // MyPhiFunction.H:14-15, :18-20
 void fill_phi(int profile, double *phi, const BoxArgs &g, double dx, const BhParams &p,
               hipStream_t st);  // an unknown profile throws kBadArg
-void binary_bh_coefs_phi(double *acoef, double *rhs, const double *psi, const double *phi,
-                         const BoxArgs &g, double dx, const BhParams &p, hipStream_t st);
-void constant_k_integrand_phi(double *out, const double *psi, const double *phi, const BoxArgs &g,
-                              double dx, const BhParams &p, hipStream_t st);
-void regrid_condition_phi(double *out, const double *psi, const double *phi, const BoxArgs &g,
-                          double dx, const BhParams &p, hipStream_t st);
-void output_vars_phi(int kind, double *out, const double *psi, const double *dpsi,
-                     const double *rhs, const double *phi, const BoxArgs &g, int k0, int nk,
-                     double dx, const BhParams &p, hipStream_t st);
 // x += y over the valid box grown by `grow` (<= kGhost) cells
 void incr_grown(double *x, const double *y, const BoxArgs &g, int grow, hipStream_t st);
 

@@ -3,7 +3,8 @@ of set_initial_conditions, SetLevelData.cpp:32-71).
 
 1. the fill kernels against the analytic path's phi_0 and the numpy formulas;
 2. the pin: with phi_0 filled by the Gaussian kernel every stored-field
-   generator gives the analytic entry point's bits;
+   generator gives the analytic entry point's bits, and the analytic entry
+   points meet the oracle with that (wide) Gaussian;
 3. any stored field: acoef is 2 pi G GETRHOGRADPHIF(stored values), ghosts
    read as stored;
 4. poisson_solve / set_grids with PhiProfile.gaussian() against today's path;
@@ -203,6 +204,51 @@ def test_stored_gaussian_path_is_bit_identical_to_analytic_path(comm, layout, wi
             nz = _shape(grid.local_box(n))[0]
             assert np.array_equal(grchombo_vars(u, n, BH, 3, nz - 4, phi=phi),
                                   grchombo_vars(u, n, BH)[:, 3:nz - 1])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_psi", [False, True], ids=["psi=None", "psi=random"])
+@pytest.mark.parametrize("layout", ["ragged", "2x2x1"])
+def test_analytic_generators_match_oracle_on_the_wide_gaussian(comm, layout, with_psi):
+    # The pin above compares two instantiations of one kernel template, so the
+    # analytic one is held to the CPU oracle here, with the Gaussian of BH
+    # (params.txt's is zero to rounding almost everywhere).  Tolerances: those
+    # of the CPU test above on these boxes -- aCoef and the regrid condition
+    # relative, rhs and the integrand (which change sign inside the boxes)
+    # against the field's largest magnitude.
+    import mg_ic_code_amd as mg
+    from mg_ic_code_amd._lib import call
+    from mg_ic_code_amd.grids import set_regrid_condition
+    from tests import regrid_ref
+    rng = np.random.default_rng(20261020)
+    (grid,) = _grids(comm, layout)
+    boxes = _boxes(grid)
+    psi_g = [1.0 + 0.05 * rng.uniform(-1, 1, _shape(b, 1)) if with_psi else np.ones(_shape(b, 1))
+             for b in boxes]
+    psi = None
+    if with_psi:
+        psi = mg.LevelData(grid)
+        for n, pg in enumerate(psi_g):
+            psi.upload(n, pg, with_ghosts=True)
+    a, r, integ, cond = (mg.LevelData(grid) for _ in range(4))
+    mg.set_nl_coefs(psi, a, r, BH)
+    call("mgic_field_nl_integrand", psi.handle if psi else None, integ.handle, _bhv(BH))
+    set_regrid_condition(psi, cond, BH)
+    for n, (b, pg) in enumerate(zip(boxes, psi_g)):
+        lo, hi = b[:3], b[3:]
+        ao, ro = oracle.nl_coefs(BH, lo, hi, grid.dx, pg if with_psi else None)
+        io = oracle.nl_integrand(BH, lo, hi, grid.dx, pg)
+        co = regrid_ref.regrid_condition(BH, lo, hi, grid.dx,
+                                         pg[1:-1, 1:-1, 1:-1] if with_psi else None)
+        got = (a.download(n), r.download(n), integ.download(n), cond.download(n))
+        print(layout, b, "max rel err: aCoef", np.max(np.abs(got[0] - ao) / np.abs(ao)),
+              "condition", np.max(np.abs(got[3] - co) / np.abs(co)),
+              "max err / max|ref|: rhs", np.max(np.abs(got[1] - ro)) / np.abs(ro).max(),
+              "integrand", np.max(np.abs(got[2] - io)) / np.abs(io).max())
+        np.testing.assert_allclose(got[0], ao, rtol=1e-13, atol=0)
+        np.testing.assert_allclose(got[3], co, rtol=1e-13, atol=0)
+        np.testing.assert_allclose(got[1], ro, rtol=0, atol=1e-13 * np.abs(ro).max())
+        np.testing.assert_allclose(got[2], io, rtol=0, atol=1e-13 * np.abs(io).max())
 
 
 @pytest.mark.gpu

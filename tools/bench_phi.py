@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Stored phi_0 against analytic phi_0: set_nl_coefs and the regrid condition.
 
-The stored-field generators (k_binary_bh_phi, k_regrid_condition_phi) load
-phi_0 from a device field -- 7 reads of one extra 8-byte stream per cell, 6 of
-them neighbours that the caches serve -- where the analytic ones
-(k_binary_bh, k_regrid_condition) evaluate six exp per cell.  Both on the
+The STORED instantiations of the generators (k_binary_bh<.., true>,
+k_regrid_condition<true>) load phi_0 from a device field -- 7 reads of one
+extra 8-byte stream per cell, 6 of them neighbours that the caches serve --
+where the analytic ones (<.., false>) evaluate six exp per cell.  Both on the
 same n^3 box, interleaved (analytic, stored, analytic, ...), each sample the
 device time of `reps` back-to-back calls between HIP events on the library's
 stream; the fill kernel (once per solve) is timed the same way.
