@@ -481,6 +481,43 @@ MGIC_API int mgic_field_grchombo_vars_phi(mgic_field psi, mgic_field phi, int n,
 MGIC_API int mgic_field_solver_vars_phi(mgic_field dpsi, mgic_field rhs, mgic_field psi,
                                         mgic_field phi, int n, int k0, int nk, const double bh[13],
                                         double *out, int out_on_device);
+/* ---- Bowen-York punctures as a table.  The entry points above place two
+ * holes on the x axis with momentum along y and spin along z (bh[4..11]).
+ * The *_punct entry points take 1 to MGIC_MAX_PUNCTURES punctures instead,
+ * each with any position, momentum and spin: `table` holds 10 doubles per
+ * puncture, in the order m, x, y, z, Px, Py, Pz, Jx, Jy, Jz, with positions
+ * relative to the domain centre (the coordinates of bh1_offset).
+ *
+ * The table is taken in pairs, in table order: (0, 1), (2, 3), ...  One pair
+ * contributes what get_Aij (SetBinaryBH.H:24-53) gives for two holes with
+ * these vectors, l_a = loc - (x_a, y_a, z_a), and psi_bh = m_a / r_a +
+ * m_b / r_b; A_ij_0 and psi_bh are the sums over the pairs in pair order,
+ * starting from the first pair's value.  An odd count is completed by a
+ * puncture with m = P = J = 0 at the last puncture's position.  Punctures get
+ * no periodic images.  So the deck's two holes written as the table
+ * {m1, off1, 0, 0, 0, mom1, 0, 0, 0, spin1, m2, off2, 0, 0, 0, mom2, 0, 0, 0,
+ * spin2} give the bits of the entry points above.
+ *
+ * bh[13] still carries the domain length, G, the phi parameters and
+ * constant_K; its six hole entries bh[4..11] are ignored.  phi: the stored
+ * phi_0 on the layout of the other fields, or NULL for the analytic Gaussian.
+ * MGIC_EBADARG, before anything is launched, for a count outside 1 ..
+ * MGIC_MAX_PUNCTURES, a NULL table or a non-finite entry. */
+#define MGIC_MAX_PUNCTURES 8
+MGIC_API int mgic_field_nl_coefs_punct(mgic_field psi, mgic_field phi, mgic_field acoef,
+                                       mgic_field rhs, const double bh[13], int n,
+                                       const double *table);
+MGIC_API int mgic_field_nl_integrand_punct(mgic_field psi, mgic_field phi, mgic_field out,
+                                           const double bh[13], int n, const double *table);
+MGIC_API int mgic_field_regrid_condition_punct(mgic_field psi, mgic_field phi, mgic_field out,
+                                               const double bh[13], int n, const double *table);
+MGIC_API int mgic_field_grchombo_vars_punct(mgic_field psi, mgic_field phi, int n, int k0, int nk,
+                                            const double bh[13], int npunct, const double *table,
+                                            double *out, int out_on_device);
+MGIC_API int mgic_field_solver_vars_punct(mgic_field dpsi, mgic_field rhs, mgic_field psi,
+                                          mgic_field phi, int n, int k0, int nk,
+                                          const double bh[13], int npunct, const double *table,
+                                          double *out, int out_on_device);
 /* the field's layout: domain, periodicity, dx, number of boxes (all ranks),
  * this rank and the job size; box i's extent, owner rank and local index
  * (-1 if not local); a barrier over the field's communicator */

@@ -66,6 +66,23 @@ MGIC_IO_API int mgic_io_write_solver_data_phi(const char *filename, int nlevels,
                                               const mgic_field *psi, const mgic_field *phi,
                                               const double bh[13], const int *ref_ratio, int iter);
 
+/* The two writers with the holes taken from a puncture table (mgic.h,
+ * "Bowen-York punctures as a table"): npunct punctures, 10 doubles each.  The
+ * A_ij and chi components of the final data and the A_ij_0 components of the
+ * solver data come from the table; bh's six hole entries are ignored.  phi:
+ * one stored phi_0 field per level, or NULL for the analytic Gaussian. */
+MGIC_IO_API int mgic_io_write_final_data_punct(const char *filename, int nlevels,
+                                               const mgic_field *psi, const mgic_field *phi,
+                                               const double bh[13], int npunct,
+                                               const double *table, int max_level,
+                                               const int *ref_ratio);
+MGIC_IO_API int mgic_io_write_solver_data_punct(const char *filename, int nlevels,
+                                                const mgic_field *dpsi, const mgic_field *rhs,
+                                                const mgic_field *psi, const mgic_field *phi,
+                                                const double bh[13], int npunct,
+                                                const double *table, const int *ref_ratio,
+                                                int iter);
+
 /* The same two layouts from host arrays (tests, and callers whose data is
  * already on the host).  kind 0: final data (31 components), 1: solver data
  * (10).  Level l has nbox[l] boxes (6 ints each, all levels concatenated in

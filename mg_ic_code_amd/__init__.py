@@ -33,5 +33,6 @@ from .grids import set_grids  # noqa: F401
 from ._lib import IO_LIB_PATH, LIB_PATH, lib  # noqa: F401
 from .output import output_final_data, output_solver_data  # noqa: F401
 from .phi import PhiProfile  # noqa: F401
+from .punctures import Puncture, PunctureSet  # noqa: F401
 
 __version__ = "0.1.0"

@@ -617,8 +617,10 @@ static kern::BhParams bh_params(const double bh[13]) {
 }
 // The generators below take phi: the stored phi_0 (the *_phi entry points,
 // which refuse a null one first), or null: evaluated in place.
+// table: the puncture table (the *_punct entry points, which check it first),
+// or null: the two holes of bh.
 static void nl_coefs_capi(mgic_field psi, mgic_field phi, mgic_field acoef, mgic_field rhs,
-                          const double bh[13]) {
+                          const double bh[13], const kern::PunctureTable *table = nullptr) {
   NEED(acoef);
   NEED(rhs);
   NEED(bh);
@@ -630,13 +632,13 @@ static void nl_coefs_capi(mgic_field psi, mgic_field phi, mgic_field acoef, mgic
   for (int n = 0; n < g.nlocal(); ++n)
     kern::binary_bh_coefs(acoef->f->p[n], rhs->f->p[n], psi ? psi->f->p[n] : nullptr,
                           phi ? phi->f->p[n] : nullptr, g.box_args_plain(n), g.dx, p,
-                          g.comm->stream());
+                          g.comm->stream(), table);
 }
 // gen: kern::constant_k_integrand or kern::regrid_condition
 using PsiGenerator = void (*)(double *, const double *, const double *, const BoxArgs &, double,
-                              const kern::BhParams &, hipStream_t);
+                              const kern::BhParams &, hipStream_t, const kern::PunctureTable *);
 static void psi_generator_capi(PsiGenerator gen, mgic_field psi, mgic_field phi, mgic_field out,
-                               const double bh[13]) {
+                               const double bh[13], const kern::PunctureTable *table = nullptr) {
   NEED(out);
   NEED(bh);
   const Grid &g = *out->f->grid;
@@ -645,7 +647,7 @@ static void psi_generator_capi(PsiGenerator gen, mgic_field psi, mgic_field phi,
   const kern::BhParams p = bh_params(bh);
   for (int n = 0; n < g.nlocal(); ++n)
     gen(out->f->p[n], psi ? psi->f->p[n] : nullptr, phi ? phi->f->p[n] : nullptr,
-        g.box_args_plain(n), g.dx, p, g.comm->stream());
+        g.box_args_plain(n), g.dx, p, g.comm->stream(), table);
 }
 MGIC_API int mgic_field_nl_coefs(mgic_field psi, mgic_field acoef, mgic_field rhs,
                                  const double bh[13]) {
@@ -679,7 +681,7 @@ static void *scratch_device(size_t bytes) {
 // phi: the stored phi_0 (the *_phi entry points), or null: evaluated in place
 static void output_vars_capi(int kind, mgic_field psi, mgic_field dpsi, mgic_field rhs, int n,
                              int k0, int nk, const double bh[13], double *out, int on_device,
-                             mgic_field phi = nullptr) {
+                             mgic_field phi = nullptr, const kern::PunctureTable *table = nullptr) {
   NEED(psi);
   NEED(bh);
   NEED(out);
@@ -703,7 +705,8 @@ static void output_vars_capi(int kind, mgic_field psi, mgic_field dpsi, mgic_fie
   double *d = out;
   if (!on_device) d = static_cast<double *>(scratch_device(bytes));
   const double *dp = kind ? dpsi->f->p[n] : nullptr, *rp = kind ? rhs->f->p[n] : nullptr;
-  kern::output_vars(kind, d, u.p[n], dp, rp, phi ? phi->f->p[n] : nullptr, a, k0, nk, g.dx, p, st);
+  kern::output_vars(kind, d, u.p[n], dp, rp, phi ? phi->f->p[n] : nullptr, a, k0, nk, g.dx, p, st,
+                    table);
   if (!on_device) {
     MGIC_HIP(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, st));
     MGIC_HIP(hipStreamSynchronize(st));
@@ -771,6 +774,55 @@ MGIC_API int mgic_field_solver_vars_phi(mgic_field dpsi, mgic_field rhs, mgic_fi
   return guard([&] {
     NEED(phi);
     output_vars_capi(1, psi, dpsi, rhs, n, k0, nk, bh, out, out_on_device, phi);
+  });
+}
+// ---- the puncture table (mgic.h, "Bowen-York punctures as a table"): the
+// generators and output components above with the holes taken from `table`
+// (10 doubles per puncture) instead of bh's six hole entries; phi null: the
+// analytic Gaussian.  The table is checked before anything else, and nothing
+// is launched when a check fails.
+static kern::PunctureTable punctures(int n, const double *table) {
+  kern::PunctureTable t;
+  kern::set_punctures(t, n, table);
+  return t;
+}
+MGIC_API int mgic_field_nl_coefs_punct(mgic_field psi, mgic_field phi, mgic_field acoef,
+                                       mgic_field rhs, const double bh[13], int n,
+                                       const double *table) {
+  return guard([&] {
+    const kern::PunctureTable t = punctures(n, table);
+    nl_coefs_capi(psi, phi, acoef, rhs, bh, &t);
+  });
+}
+MGIC_API int mgic_field_nl_integrand_punct(mgic_field psi, mgic_field phi, mgic_field out,
+                                           const double bh[13], int n, const double *table) {
+  return guard([&] {
+    const kern::PunctureTable t = punctures(n, table);
+    psi_generator_capi(kern::constant_k_integrand, psi, phi, out, bh, &t);
+  });
+}
+MGIC_API int mgic_field_regrid_condition_punct(mgic_field psi, mgic_field phi, mgic_field out,
+                                               const double bh[13], int n, const double *table) {
+  return guard([&] {
+    const kern::PunctureTable t = punctures(n, table);
+    psi_generator_capi(kern::regrid_condition, psi, phi, out, bh, &t);
+  });
+}
+MGIC_API int mgic_field_grchombo_vars_punct(mgic_field psi, mgic_field phi, int n, int k0, int nk,
+                                            const double bh[13], int npunct, const double *table,
+                                            double *out, int out_on_device) {
+  return guard([&] {
+    const kern::PunctureTable t = punctures(npunct, table);
+    output_vars_capi(0, psi, nullptr, nullptr, n, k0, nk, bh, out, out_on_device, phi, &t);
+  });
+}
+MGIC_API int mgic_field_solver_vars_punct(mgic_field dpsi, mgic_field rhs, mgic_field psi,
+                                          mgic_field phi, int n, int k0, int nk,
+                                          const double bh[13], int npunct, const double *table,
+                                          double *out, int out_on_device) {
+  return guard([&] {
+    const kern::PunctureTable t = punctures(npunct, table);
+    output_vars_capi(1, psi, dpsi, rhs, n, k0, nk, bh, out, out_on_device, phi, &t);
   });
 }
 MGIC_API int mgic_field_norm(mgic_field x, int ord, double *out) {

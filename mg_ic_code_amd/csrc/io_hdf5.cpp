@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdio>
 #include <functional>
 #include <map>
@@ -375,9 +376,11 @@ MGIC_IO_API const char *mgic_io_last_error(void) { return g_err.c_str(); }
 namespace {
 
 // phi: null (phi_0 evaluated in place), or one stored phi_0 field per level
+// table: null (the two holes of bh), or npunct punctures of 10 doubles each;
+// the library checks it at the first box, before it launches anything
 int write_final_data(const char *filename, int nlevels, const mgic_field *psi,
                      const mgic_field *phi, const double bh[13], int max_level,
-                     const int *ref_ratio) {
+                     const int *ref_ratio, int npunct = 0, const double *table = nullptr) {
   return guard([&] {
     need(psi, "psi");
     need(bh, "bh");
@@ -393,7 +396,10 @@ int write_final_data(const char *filename, int nlevels, const mgic_field *psi,
     for (int l = 0; phi && l < nlevels; ++l) need(phi[l], "phi[l]");
     write_fields(filename ? filename : "vcPoissonFinal.3d.hdf5", J, lead,
                  [&](int l, int n, int k0, int nk, double *out) {
-                   if (phi)
+                   if (table)
+                     mg(mgic_field_grchombo_vars_punct(psi[l], phi ? phi[l] : nullptr, n, k0, nk,
+                                                       bh, npunct, table, out, 0));
+                   else if (phi)
                      mg(mgic_field_grchombo_vars_phi(psi[l], phi[l], n, k0, nk, bh, out, 0));
                    else
                      mg(mgic_field_grchombo_vars(psi[l], n, k0, nk, bh, out, 0));
@@ -403,7 +409,8 @@ int write_final_data(const char *filename, int nlevels, const mgic_field *psi,
 
 int write_solver_data(const char *filename, int nlevels, const mgic_field *dpsi,
                       const mgic_field *rhs, const mgic_field *psi, const mgic_field *phi,
-                      const double bh[13], const int *ref_ratio, int iter) {
+                      const double bh[13], const int *ref_ratio, int iter, int npunct = 0,
+                      const double *table = nullptr) {
   return guard([&] {
     need(dpsi, "dpsi");
     need(rhs, "rhs");
@@ -426,7 +433,10 @@ int write_solver_data(const char *filename, int nlevels, const mgic_field *dpsi,
     char name[64];
     std::snprintf(name, sizeof name, "vcPoissonOut.3d_%d.hdf5", iter);  // WriteOutput.H:63-70
     write_fields(filename ? filename : name, J, lead, [&](int l, int n, int k0, int nk, double *out) {
-      if (phi)
+      if (table)
+        mg(mgic_field_solver_vars_punct(dpsi[l], rhs[l], psi[l], phi ? phi[l] : nullptr, n, k0, nk,
+                                        bh, npunct, table, out, 0));
+      else if (phi)
         mg(mgic_field_solver_vars_phi(dpsi[l], rhs[l], psi[l], phi[l], n, k0, nk, bh, out, 0));
       else
         mg(mgic_field_solver_vars(dpsi[l], rhs[l], psi[l], n, k0, nk, bh, out, 0));
@@ -466,6 +476,41 @@ MGIC_IO_API int mgic_io_write_solver_data_phi(const char *filename, int nlevels,
                                               int iter) {
   if (!phi) return guard([&] { need(phi, "phi"); });
   return write_solver_data(filename, nlevels, dpsi, rhs, psi, phi, bh, ref_ratio, iter);
+}
+
+// a table is refused here, before the file is created: the count, a null
+// table and non-finite entries (the library checks again per box)
+static void check_punctures(int npunct, const double *table) {
+  if (npunct < 1 || npunct > MGIC_MAX_PUNCTURES)
+    throw IoError(MGIC_EBADARG, "puncture count " + std::to_string(npunct) + " outside 1.." +
+                                    std::to_string(MGIC_MAX_PUNCTURES));
+  need(table, "punctures");
+  for (int i = 0; i < 10 * npunct; ++i)
+    if (!std::isfinite(table[i]))
+      throw IoError(MGIC_EBADARG, "puncture " + std::to_string(i / 10 + 1) + ": entry " +
+                                      std::to_string(i % 10) + " is not finite");
+}
+
+MGIC_IO_API int mgic_io_write_final_data_punct(const char *filename, int nlevels,
+                                               const mgic_field *psi, const mgic_field *phi,
+                                               const double bh[13], int npunct,
+                                               const double *table, int max_level,
+                                               const int *ref_ratio) {
+  const int st = guard([&] { check_punctures(npunct, table); });
+  if (st != MGIC_OK) return st;
+  return write_final_data(filename, nlevels, psi, phi, bh, max_level, ref_ratio, npunct, table);
+}
+
+MGIC_IO_API int mgic_io_write_solver_data_punct(const char *filename, int nlevels,
+                                                const mgic_field *dpsi, const mgic_field *rhs,
+                                                const mgic_field *psi, const mgic_field *phi,
+                                                const double bh[13], int npunct,
+                                                const double *table, const int *ref_ratio,
+                                                int iter) {
+  const int st = guard([&] { check_punctures(npunct, table); });
+  if (st != MGIC_OK) return st;
+  return write_solver_data(filename, nlevels, dpsi, rhs, psi, phi, bh, ref_ratio, iter, npunct,
+                           table);
 }
 
 MGIC_IO_API int mgic_io_write_host(const char *filename, int kind, int nlevels, const int *nbox,

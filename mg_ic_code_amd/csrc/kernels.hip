@@ -7,6 +7,7 @@
 // wavefronts along x so every wave touches whole 128-byte lines.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <type_traits>
 
 #include "kernels.hpp"
@@ -930,6 +931,68 @@ __device__ __forceinline__ double bh_A2(const BhBowenYork &c) {
          2 * pow(c.A13, 2.0) + 2 * pow(c.A23, 2.0);
 }
 
+// ---- the puncture table (kernels.hpp PunctureTable): the same Bowen-York
+// terms with the holes' positions, momenta and spins taken from a table of
+// full vectors.  One pair (a, b) of table rows is get_Aij's two holes:
+// bh_Aij with l = loc - x, P and J as stored, psi_bh = m_a / r_a + m_b / r_b.
+__device__ __forceinline__ BhBowenYork bh_pair(const double loc[3], const double *a,
+                                               const double *b) {
+  const double l1[3] = {loc[0] - a[1], loc[1] - a[2], loc[2] - a[3]};
+  const double l2[3] = {loc[0] - b[1], loc[1] - b[2], loc[2] - b[3]};
+  const double r1 = sqrt(l1[0] * l1[0] + l1[1] * l1[1] + l1[2] * l1[2]);
+  const double r2 = sqrt(l2[0] * l2[0] + l2[1] * l2[1] + l2[2] * l2[2]);
+  const double n1[3] = {l1[0] / r1, l1[1] / r1, l1[2] / r1};
+  const double n2[3] = {l2[0] / r2, l2[1] / r2, l2[2] / r2};
+  const double P1[3] = {a[4], a[5], a[6]}, P2[3] = {b[4], b[5], b[6]};
+  const double J1[3] = {a[7], a[8], a[9]}, J2[3] = {b[7], b[8], b[9]};
+  BhBowenYork c;
+  c.A11 = bh_Aij(0, 0, r1, r2, n1, n2, J1, J2, P1, P2);
+  c.A22 = bh_Aij(1, 1, r1, r2, n1, n2, J1, J2, P1, P2);
+  c.A33 = bh_Aij(2, 2, r1, r2, n1, n2, J1, J2, P1, P2);
+  c.A12 = bh_Aij(0, 1, r1, r2, n1, n2, J1, J2, P1, P2);
+  c.A13 = bh_Aij(0, 2, r1, r2, n1, n2, J1, J2, P1, P2);
+  c.A23 = bh_Aij(1, 2, r1, r2, n1, n2, J1, J2, P1, P2);
+  c.psi_bh = a[0] / r1 + b[0] / r2;
+  return c;
+}
+// A_ij_0 and psi_bh are the sums over the table's pairs (0, 1), (2, 3), ...
+// in that order, the first pair's value being the sum's first value (so the
+// deck's two holes as a table give bh_bowen_york(p, ..)'s bits).  The host
+// completes an odd count (PunctureTable).  The table is a kernel argument and
+// is indexed by the loop counter alone: wave-uniform scalar loads, no
+// register array.
+__device__ __forceinline__ BhBowenYork bh_bowen_york(const BhParams &p, const PunctureTable &t,
+                                                     const int iv[3], double dx) {
+  double loc[3];
+  for (int d = 0; d < 3; ++d) loc[d] = bh_loc(iv[d], dx, p.domlen[d]);
+  BhBowenYork c = bh_pair(loc, t.v[0], t.v[1]);
+  const int npairs = (t.n + 1) / 2;
+  for (int q = 1; q < npairs; ++q) {
+    const BhBowenYork e = bh_pair(loc, t.v[2 * q], t.v[2 * q + 1]);
+    c.A11 += e.A11;
+    c.A12 += e.A12;
+    c.A13 += e.A13;
+    c.A22 += e.A22;
+    c.A23 += e.A23;
+    c.A33 += e.A33;
+    c.psi_bh += e.psi_bh;
+  }
+  return c;
+}
+// where a generator takes the holes from, chosen at compile time.  TABLE: the
+// puncture table `t`; else the two holes of BhParams, `t` empty and unused.
+template <bool TABLE> struct PunctureArg { };
+template <> struct PunctureArg<true> { PunctureTable t; };
+template <bool TABLE>
+__device__ __forceinline__ BhBowenYork bh_terms(const BhParams &p, const PunctureArg<TABLE> &t,
+                                                const int iv[3], double dx) {
+  if constexpr (TABLE) {
+    return bh_bowen_york(p, t.t, iv, dx);
+  } else {
+    return bh_bowen_york(p, iv, dx);
+  }
+}
+
 // GETRHOGRADPHIF (SetLevelDataF.ChF:65-103) of a stored field at one cell,
 // the field's ghost layer read as is
 __device__ __forceinline__ double phi_rho_grad(const double *__restrict__ phi, long idx,
@@ -983,12 +1046,14 @@ __device__ __forceinline__ double bh_rho_grad(const BhParams &p, const double *_
 // INTEGRAND: set_constant_K_integrand (SetLevelData.cpp:131-180) into acoef
 // instead (m taken at K = 0, rhs untouched)
 // STORED: phi_0 read from `phi` with its ghost layer (see bh_phi0)
-template <bool INTEGRAND, bool STORED>
+// TABLE: the holes of the puncture table `t` (see bh_terms)
+template <bool INTEGRAND, bool STORED, bool TABLE>
 __global__ __launch_bounds__(256) void k_binary_bh(double *__restrict__ acoef,
                                                    double *__restrict__ rhs,
                                                    const double *__restrict__ psi,
                                                    const double *__restrict__ phi,
-                                                   const BoxArgs g, double dx, const BhParams p) {
+                                                   const BoxArgs g, double dx, const BhParams p,
+                                                   const PunctureArg<TABLE> t) {
   const int i = blockIdx.x * TX + threadIdx.x;
   const int j = blockIdx.y * TY + threadIdx.y;
   const int k = blockIdx.z;
@@ -996,7 +1061,7 @@ __global__ __launch_bounds__(256) void k_binary_bh(double *__restrict__ acoef,
   const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k};
   const long idx = (long)i + (long)j * g.sy + (long)k * g.sz;
   const double rho_grad = bh_rho_grad<STORED>(p, phi, iv, idx, g, dx);
-  const BhBowenYork c = bh_bowen_york(p, iv, dx);
+  const BhBowenYork c = bh_terms<TABLE>(p, t, iv, dx);
   const double A2 = bh_A2(c);
   const double rho = 0.5 * 0.0 * 0.0 + 0.0;
   const double K = INTEGRAND ? 0.0 : p.constant_K;  // set_m_value(.., 0.0) for the integrand
@@ -1026,12 +1091,14 @@ __global__ __launch_bounds__(256) void k_binary_bh(double *__restrict__ acoef,
 // psi_0 as in k_binary_bh; psi == nullptr: psi = 1 (set_grids evaluates it
 // right after set_initial_conditions).  No ghost cell of psi is read.
 // STORED: phi_0 read from `phi` with its ghost layer (see bh_phi0)
-template <bool STORED>
+// TABLE: the holes of the puncture table `t` (see bh_terms)
+template <bool STORED, bool TABLE>
 __global__ __launch_bounds__(256) void k_regrid_condition(double *__restrict__ out,
                                                           const double *__restrict__ psi,
                                                           const double *__restrict__ phi,
                                                           const BoxArgs g, double dx,
-                                                          const BhParams p) {
+                                                          const BhParams p,
+                                                          const PunctureArg<TABLE> t) {
   const int i = blockIdx.x * TX + threadIdx.x;
   const int j = blockIdx.y * TY + threadIdx.y;
   const int k = blockIdx.z;
@@ -1039,7 +1106,7 @@ __global__ __launch_bounds__(256) void k_regrid_condition(double *__restrict__ o
   const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k};
   const long idx = (long)i + (long)j * g.sy + (long)k * g.sz;
   const double rho_grad = bh_rho_grad<STORED>(p, phi, iv, idx, g, dx);
-  const BhBowenYork c = bh_bowen_york(p, iv, dx);
+  const BhBowenYork c = bh_terms<TABLE>(p, t, iv, dx);
   const double A2 = bh_A2(c);
   const double rho = 0.5 * 0.0 * 0.0 + 0.0;
   const double m = (2.0 / 3.0) * (0.0 * 0.0) - 16.0 * M_PI * p.G_Newton * rho;  // K = 0 (:219)
@@ -1136,20 +1203,22 @@ __global__ __launch_bounds__(256) void k_rho_grad_phi(double *__restrict__ r,
 //         the 8 multigrid_vars (psi, A11_0 .. A33_0, phi_0; the A_ij_0 and
 //         phi_0 of set_initial_conditions, SetLevelData.cpp:31-72)
 // STORED: phi (KIND 0, v[25]) / phi_0 (KIND 1) copied from `phi` (see bh_phi0)
-template <int KIND, bool STORED>
+// TABLE: the holes of the puncture table `t` (see bh_terms)
+template <int KIND, bool STORED, bool TABLE>
 __global__ __launch_bounds__(256) void k_output_vars(double *__restrict__ out,
                                                      const double *__restrict__ psi,
                                                      const double *__restrict__ dpsi,
                                                      const double *__restrict__ rhs,
                                                      const double *__restrict__ phi,
                                                      const BoxArgs g, int k0, int nk, double dx,
-                                                     const BhParams p) {
+                                                     const BhParams p,
+                                                     const PunctureArg<TABLE> t) {
   const int i = blockIdx.x * TX + threadIdx.x;
   const int j = blockIdx.y * TY + threadIdx.y;
   const int k = blockIdx.z;
   if (i >= g.nx || j >= g.ny) return;
   const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k0 + k};
-  const BhBowenYork b = bh_bowen_york(p, iv, dx);
+  const BhBowenYork b = bh_terms<TABLE>(p, t, iv, dx);
   const long idx = (long)i + (long)j * g.sy + (long)(k0 + k) * g.sz;
   const double phi0 = bh_phi0<STORED>(p, phi, iv, idx, dx);  // MyPhiFunction.H
   const double psi_c = psi[idx];
@@ -2055,36 +2124,86 @@ void copy_items(const CopyItem *d_items, int nitems, long max_cells, double *con
   check_launch();
 }
 
+// the generators' instantiation is picked here: phi null or stored, table
+// null (the two holes of BhParams) or given; no kernel tests either
+static void check_table(const PunctureTable *t) {
+  if (t && (t->n < 1 || t->n > kMaxPunctures))
+    throw Error(kBadArg, "puncture count " + std::to_string(t->n) + " outside 1.." +
+                             std::to_string(kMaxPunctures));
+}
+void set_punctures(PunctureTable &t, int n, const double *values) {
+  if (n < 1 || n > kMaxPunctures)
+    throw Error(kBadArg, "puncture count " + std::to_string(n) + " outside 1.." +
+                             std::to_string(kMaxPunctures));
+  if (!values) throw Error(kBadArg, "null argument: punctures");
+  for (int i = 0; i < n * kPunctureDoubles; ++i)
+    if (!std::isfinite(values[i]))
+      throw Error(kBadArg, "puncture " + std::to_string(i / kPunctureDoubles + 1) + ": entry " +
+                               std::to_string(i % kPunctureDoubles) + " is not finite");
+  t.n = n;
+  for (int q = 0; q < kMaxPunctures; ++q)
+    for (int c = 0; c < kPunctureDoubles; ++c)
+      t.v[q][c] = q < n ? values[q * kPunctureDoubles + c] : 0.0;
+  if (n % 2)  // the odd count's partner: nothing at the last puncture's position
+    for (int c = 1; c <= 3; ++c) t.v[n][c] = t.v[n - 1][c];
+}
+static PunctureArg<true> table_arg(const PunctureTable *t) {
+  PunctureArg<true> a;
+  a.t = *t;
+  return a;
+}
+
 template <bool INTEGRAND>
 static void launch_binary_bh(double *acoef, double *rhs, const double *psi, const double *phi,
-                             const BoxArgs &g, double dx, const BhParams &p, hipStream_t st) {
+                             const BoxArgs &g, double dx, const BhParams &p,
+                             const PunctureTable *t, hipStream_t st) {
+  check_table(t);
   if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
   const dim3 grid = grid_cells(g.nx, g.ny, g.nz);
-  if (phi)
-    k_binary_bh<INTEGRAND, true><<<grid, kBlock, 0, st>>>(acoef, rhs, psi, phi, g, dx, p);
+  const PunctureArg<false> none;
+  if (t && phi)
+    k_binary_bh<INTEGRAND, true, true><<<grid, kBlock, 0, st>>>(acoef, rhs, psi, phi, g, dx, p,
+                                                                table_arg(t));
+  else if (t)
+    k_binary_bh<INTEGRAND, false, true><<<grid, kBlock, 0, st>>>(acoef, rhs, psi, nullptr, g, dx,
+                                                                 p, table_arg(t));
+  else if (phi)
+    k_binary_bh<INTEGRAND, true, false><<<grid, kBlock, 0, st>>>(acoef, rhs, psi, phi, g, dx, p,
+                                                                 none);
   else
-    k_binary_bh<INTEGRAND, false><<<grid, kBlock, 0, st>>>(acoef, rhs, psi, nullptr, g, dx, p);
+    k_binary_bh<INTEGRAND, false, false><<<grid, kBlock, 0, st>>>(acoef, rhs, psi, nullptr, g, dx,
+                                                                  p, none);
   check_launch();
 }
 
 void binary_bh_coefs(double *acoef, double *rhs, const double *psi, const double *phi,
-                     const BoxArgs &g, double dx, const BhParams &p, hipStream_t st) {
-  launch_binary_bh<false>(acoef, rhs, psi, phi, g, dx, p, st);
+                     const BoxArgs &g, double dx, const BhParams &p, hipStream_t st,
+                     const PunctureTable *table) {
+  launch_binary_bh<false>(acoef, rhs, psi, phi, g, dx, p, table, st);
 }
 
 void constant_k_integrand(double *out, const double *psi, const double *phi, const BoxArgs &g,
-                          double dx, const BhParams &p, hipStream_t st) {
-  launch_binary_bh<true>(out, nullptr, psi, phi, g, dx, p, st);
+                          double dx, const BhParams &p, hipStream_t st,
+                          const PunctureTable *table) {
+  launch_binary_bh<true>(out, nullptr, psi, phi, g, dx, p, table, st);
 }
 
 void regrid_condition(double *out, const double *psi, const double *phi, const BoxArgs &g,
-                      double dx, const BhParams &p, hipStream_t st) {
+                      double dx, const BhParams &p, hipStream_t st, const PunctureTable *table) {
+  check_table(table);
   if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
   const dim3 grid = grid_cells(g.nx, g.ny, g.nz);
-  if (phi)
-    k_regrid_condition<true><<<grid, kBlock, 0, st>>>(out, psi, phi, g, dx, p);
+  const PunctureArg<false> none;
+  if (table && phi)
+    k_regrid_condition<true, true><<<grid, kBlock, 0, st>>>(out, psi, phi, g, dx, p,
+                                                            table_arg(table));
+  else if (table)
+    k_regrid_condition<false, true><<<grid, kBlock, 0, st>>>(out, psi, nullptr, g, dx, p,
+                                                             table_arg(table));
+  else if (phi)
+    k_regrid_condition<true, false><<<grid, kBlock, 0, st>>>(out, psi, phi, g, dx, p, none);
   else
-    k_regrid_condition<false><<<grid, kBlock, 0, st>>>(out, psi, nullptr, g, dx, p);
+    k_regrid_condition<false, false><<<grid, kBlock, 0, st>>>(out, psi, nullptr, g, dx, p, none);
   check_launch();
 }
 
@@ -2120,23 +2239,33 @@ void rho_grad_phi(double *r, const double *phi, const BoxArgs &g, double dx, hip
 template <int KIND>
 static void launch_output_vars(double *out, const double *psi, const double *dpsi,
                                const double *rhs, const double *phi, const BoxArgs &g, int k0,
-                               int nk, double dx, const BhParams &p, hipStream_t st) {
+                               int nk, double dx, const BhParams &p, const PunctureTable *t,
+                               hipStream_t st) {
   const dim3 grid = grid_cells(g.nx, g.ny, nk);
-  if (phi)
-    k_output_vars<KIND, true><<<grid, kBlock, 0, st>>>(out, psi, dpsi, rhs, phi, g, k0, nk, dx, p);
+  const PunctureArg<false> none;
+  if (t && phi)
+    k_output_vars<KIND, true, true><<<grid, kBlock, 0, st>>>(out, psi, dpsi, rhs, phi, g, k0, nk,
+                                                             dx, p, table_arg(t));
+  else if (t)
+    k_output_vars<KIND, false, true><<<grid, kBlock, 0, st>>>(out, psi, dpsi, rhs, nullptr, g, k0,
+                                                              nk, dx, p, table_arg(t));
+  else if (phi)
+    k_output_vars<KIND, true, false><<<grid, kBlock, 0, st>>>(out, psi, dpsi, rhs, phi, g, k0, nk,
+                                                              dx, p, none);
   else
-    k_output_vars<KIND, false><<<grid, kBlock, 0, st>>>(out, psi, dpsi, rhs, nullptr, g, k0, nk,
-                                                        dx, p);
+    k_output_vars<KIND, false, false><<<grid, kBlock, 0, st>>>(out, psi, dpsi, rhs, nullptr, g,
+                                                               k0, nk, dx, p, none);
 }
 
 void output_vars(int kind, double *out, const double *psi, const double *dpsi, const double *rhs,
                  const double *phi, const BoxArgs &g, int k0, int nk, double dx, const BhParams &p,
-                 hipStream_t st) {
+                 hipStream_t st, const PunctureTable *table) {
+  check_table(table);
   if (g.nx <= 0 || g.ny <= 0 || nk <= 0) return;
   if (kind == 0)
-    launch_output_vars<0>(out, psi, dpsi, rhs, phi, g, k0, nk, dx, p, st);
+    launch_output_vars<0>(out, psi, dpsi, rhs, phi, g, k0, nk, dx, p, table, st);
   else
-    launch_output_vars<1>(out, psi, dpsi, rhs, phi, g, k0, nk, dx, p, st);
+    launch_output_vars<1>(out, psi, dpsi, rhs, phi, g, k0, nk, dx, p, table, st);
   check_launch();
 }
 

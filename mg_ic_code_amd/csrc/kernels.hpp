@@ -201,18 +201,39 @@ struct BhParams {
   double G_Newton, phi_amplitude, phi_wavelength;
   double m1, m2, spin1, spin2, off1, off2, mom1, mom2, constant_K;
 };
+// The puncture table: n (1 .. kMaxPunctures) Bowen-York punctures, each row
+// m, x, y, z, Px, Py, Pz, Jx, Jy, Jz; positions relative to the domain centre
+// (the coordinates of the cell centres, as BhParams::off1).  The generators
+// take the rows in pairs (0, 1), (2, 3), ...: a pair is get_Aij's two holes
+// with full vectors, and A_ij_0 and psi_bh are the sums over the pairs in that
+// order.  An odd n is completed by set_punctures with a row of m = P = J = 0
+// at the last puncture's position (its terms are +-0).  648 bytes, passed to
+// the kernels by value.
+constexpr int kMaxPunctures = 8, kPunctureDoubles = 10;
+struct PunctureTable {
+  int n;
+  double v[kMaxPunctures][kPunctureDoubles];
+};
+// fill t from 10 n values in row order; throws kBadArg on a count outside
+// 1 .. kMaxPunctures, a null `values` or a non-finite entry
+void set_punctures(PunctureTable &t, int n, const double *values);
 // psi: nullptr = psi 1 everywhere, else read with its ghost layer
+// table (here and below): nullptr = the two holes of BhParams, else the
+// puncture table (the six hole entries of BhParams are then unused)
 // phi (here and in the generators below): nullptr = phi_0 is MyPhiFunction.H's
 // Gaussian evaluated in place, else the stored phi_0 (see fill_phi), read with
 // its one ghost layer next to each face
 void binary_bh_coefs(double *acoef, double *rhs, const double *psi, const double *phi,
-                     const BoxArgs &g, double dx, const BhParams &p, hipStream_t st);
+                     const BoxArgs &g, double dx, const BhParams &p, hipStream_t st,
+                     const PunctureTable *table = nullptr);
 // set_constant_K_integrand (SetLevelData.cpp:131-180) at psi (nullptr: 1)
 void constant_k_integrand(double *out, const double *psi, const double *phi, const BoxArgs &g,
-                          double dx, const BhParams &p, hipStream_t st);
+                          double dx, const BhParams &p, hipStream_t st,
+                          const PunctureTable *table = nullptr);
 // set_regrid_condition (SetLevelData.cpp:190-240) at psi (nullptr: 1)
 void regrid_condition(double *out, const double *psi, const double *phi, const BoxArgs &g,
-                      double dx, const BhParams &p, hipStream_t st);
+                      double dx, const BhParams &p, hipStream_t st,
+                      const PunctureTable *table = nullptr);
 // set_tag_cells (SetGrids.cpp:172-207) of one box onto a byte mask over lattice
 // cells [lat_lo, lat_lo + lat_n) (lattice index = floor(cell / c), x fastest):
 // cells with |cond| >= tag_val, grown by `grow` and clipped to [dom_lo,
@@ -230,7 +251,7 @@ void rho_grad_phi(double *r, const double *phi, const BoxArgs &g, double dx, hip
 constexpr int kNumGRChomboVars = 31, kNumSolverVars = 10;
 void output_vars(int kind, double *out, const double *psi, const double *dpsi, const double *rhs,
                  const double *phi, const BoxArgs &g, int k0, int nk, double dx, const BhParams &p,
-                 hipStream_t st);
+                 hipStream_t st, const PunctureTable *table = nullptr);
 // ---- phi_0 as a stored field (SetLevelData.cpp:32-71's c_phi_0): the profile
 // at every cell centre of the box grown by one, for the generators' `phi`
 enum PhiProfile { kPhiGaussian = 0, kPhiSine = 1 };  // MyPhiFunction.H:14-15, :18-20

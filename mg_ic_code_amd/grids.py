@@ -32,6 +32,7 @@ from ._lib import call
 from .core import BH_KEYS, Box6, Grid, LevelData, _ints, gloo_allgather
 from .params import PoissonParameters
 from .phi import PhiArgumentError, PhiProfile, set_regrid_condition_phi
+from .punctures import resolve_punctures, set_regrid_condition_punct
 
 TAGS_GROW = 2        # SetGrids.cpp:109
 NESTING_RADIUS = 2   # SetGrids.cpp:64
@@ -130,7 +131,7 @@ def _level_max_norm(cond: LevelData) -> float:
 
 
 def set_grids(comm, prm: PoissonParameters, base_grid: Grid, max_level: Optional[int] = None,
-              allgather=None, phi0: Optional[PhiProfile] = None) -> List[Grid]:
+              allgather=None, phi0: Optional[PhiProfile] = None, punctures=None) -> List[Grid]:
     """The hierarchy set_grids generates over `base_grid` (level 0, covering
     the domain): [base_grid, Grid(patches=True) of level 1, ...], at most
     max_level (default prm.max_level) levels above the base.  comm.size > 1:
@@ -138,10 +139,14 @@ def set_grids(comm, prm: PoissonParameters, base_grid: Grid, max_level: Optional
     rank]` (default gloo_allgather()); every rank returns the same hierarchy.
     phi0: None -- the analytic Gaussian; else a PhiProfile, stored on every
     level of every pass (new levels appear, so pre-filled fields cannot be
-    taken) and read by the stored-field regrid condition."""
+    taken) and read by the stored-field regrid condition.
+    punctures: None -- the deck's table (prm.punctures) if it has one, else the
+    deck's two holes; else a punctures.PunctureSet, read by the table form of
+    the regrid condition."""
     if phi0 is not None and not isinstance(phi0, PhiProfile):
         raise PhiArgumentError("set_grids", "phi0 must be a PhiProfile (levels appear and must "
                                f"be filled), not {type(phi0).__name__}")
+    punct = resolve_punctures(punctures, prm)
     max_level = prm.max_level if max_level is None else int(max_level)
     c, _ = regrid_lattice(prm.block_factor, prm.max_grid_size)
     if comm.size > 1 and allgather is None:
@@ -156,7 +161,10 @@ def set_grids(comm, prm: PoissonParameters, base_grid: Grid, max_level: Optional
         tags = []
         for g in grids:
             cond = LevelData(g)
-            if phi0 is None:
+            if punct is not None:
+                set_regrid_condition_punct(None, cond, bh, punct,
+                                           phi=phi0.fill(g, bh) if phi0 is not None else None)
+            elif phi0 is None:
                 set_regrid_condition(None, cond, bh)
             else:
                 set_regrid_condition_phi(None, phi0.fill(g, bh), cond, bh)

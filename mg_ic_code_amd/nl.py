@@ -48,6 +48,7 @@ from ._lib import call
 from .output import output_final_data, output_solver_data
 from .params import PoissonParameters
 from .phi import resolve_phi0, set_nl_coefs_phi, set_nl_integrand_phi
+from .punctures import resolve_punctures, set_nl_coefs_punct, set_nl_integrand_punct
 
 
 # Main_PoissonSolver.cpp:221-225: "a fairly generous threshold"
@@ -80,16 +81,21 @@ def set_nl_integrand(psi: LevelData, out: LevelData, bh: dict) -> None:
     call("mgic_field_nl_integrand", psi.handle, out.handle, vals)
 
 
-def _coefs(psi, phi, a, rhs, bh) -> None:
-    """set_a_coef + set_rhs: analytic phi_0 (phi None) or the stored field."""
-    if phi is None:
+def _coefs(psi, phi, a, rhs, bh, punct=None) -> None:
+    """set_a_coef + set_rhs: analytic phi_0 (phi None) or the stored field; the
+    deck's two holes (punct None) or the puncture table."""
+    if punct is not None:
+        set_nl_coefs_punct(psi, a, rhs, bh, punct, phi=phi)
+    elif phi is None:
         set_nl_coefs(psi, a, rhs, bh)
     else:
         set_nl_coefs_phi(psi, phi, a, rhs, bh)
 
 
-def _integrand(psi, phi, out, bh) -> None:
-    if phi is None:
+def _integrand(psi, phi, out, bh, punct=None) -> None:
+    if punct is not None:
+        set_nl_integrand_punct(psi, out, bh, punct, phi=phi)
+    elif phi is None:
         set_nl_integrand(psi, out, bh)
     else:
         set_nl_integrand_phi(psi, phi, out, bh)
@@ -98,15 +104,20 @@ def _integrand(psi, phi, out, bh) -> None:
 def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
                   prolong_type: int = 1, bottom_solver: int = 1,
                   max_NL_iterations: Optional[int] = None,
-                  output_dir: Optional[str] = None, phi0=None) -> NLResult:
+                  output_dir: Optional[str] = None, phi0=None, punctures=None) -> NLResult:
     """phi0: None -- the analytic Gaussian, evaluated in the kernels; else a
     phi.PhiProfile, or one pre-filled LevelData per level: phi_0 is stored once
     before the NL loop (set_initial_conditions, SetLevelData.cpp:32-71) and the
-    stored-field generators and writers are used throughout."""
+    stored-field generators and writers are used throughout.
+    punctures: None -- the deck's table (prm.punctures) if it has one, else
+    the deck's two holes through today's entry points; else a
+    punctures.PunctureSet: the table generators and writers are used
+    throughout."""
+    punct = resolve_punctures(punctures, prm)
     if isinstance(grid, (list, tuple)):
         if len(grid) > 1:
             return _poisson_solve_amr(list(grid), prm, max_depth, prolong_type, bottom_solver,
-                                      max_NL_iterations, output_dir, phi0)
+                                      max_NL_iterations, output_dir, phi0, punct)
         grid = grid[0]
     phis = resolve_phi0(phi0, [grid], prm)
     phi = phis[0] if phis is not None else None
@@ -136,12 +147,12 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
                 integrand, ones = LevelData(grid), LevelData(grid)
                 ones.set_val(1.0)
             bh["constant_K"] = 0.0
-            _integrand(psi, phi, integrand, bh)
+            _integrand(psi, phi, integrand, bh, punct)
             tmp_op = defineOperatorFactory(grid, a, b, op_params).AMRnewOp()
             integral = tmp_op.dotProduct(integrand, ones) * dx ** 3  # computeSum
             bh["constant_K"] = -math.sqrt(abs(integral) / volume)
             res.constant_K.append(bh["constant_K"])
-        _coefs(psi, phi, a, rhs, bh)  # :155-161
+        _coefs(psi, phi, a, rhs, bh, punct)  # :155-161
         fac = defineOperatorFactory(grid, a, b, op_params)
         # N > 1: depths whose boxes are below 32 cells a side are gathered to
         # one box on rank 0 (the coarsest levels solved on rank 0)
@@ -154,7 +165,8 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
                                 norm_type=0)
         if output_dir is not None:  # :180-181
             output_solver_data([dpsi], [rhs], [psi], bh, it, [2],
-                               os.path.join(output_dir, f"vcPoissonOut.3d_{it}.hdf5"), phi=phis)
+                               os.path.join(output_dir, f"vcPoissonOut.3d_{it}.hdf5"), phi=phis,
+                               punctures=punct)
         res.linear_iterations.append(solver.solve(dpsi, rhs))
         op0 = amg.op(0)
         op0.update_psi(psi, dpsi)
@@ -168,7 +180,8 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
     if output_dir is not None:  # :227-230
         def write():
             output_final_data([psi], bh, prm.max_level, [2],
-                              os.path.join(output_dir, "vcPoissonFinal.3d.hdf5"), phi=phis)
+                              os.path.join(output_dir, "vcPoissonFinal.3d.hdf5"), phi=phis,
+                              punctures=punct)
     return finish_nl_loop(res, write)
 
 
@@ -181,7 +194,7 @@ def _op_params(prm: PoissonParameters, prolong_type: int) -> OperatorParams:
 
 def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int,
                        prolong_type: int, bottom_solver: int, max_NL_iterations: Optional[int],
-                       output_dir: Optional[str], phi0=None) -> NLResult:
+                       output_dir: Optional[str], phi0=None, punct=None) -> NLResult:
     """poissonSolve over nlevels = len(grids) AMR levels (Main_PoissonSolver.cpp:51-250)."""
     periodic = bool(prm.is_periodic)
     if periodic != all(grids[0].periodic):
@@ -217,19 +230,20 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
                 geom = AMRSolver(list(zip(grids, a, b)), op_params, sp)
             bh["constant_K"] = 0.0
             for l in range(nlev):
-                _integrand(psi[l], phi[l], integrand[l], bh)
+                _integrand(psi[l], phi[l], integrand[l], bh, punct)
             integral = geom.computeSum(integrand)
             bh["constant_K"] = -math.sqrt(abs(integral) / volume)
             res.constant_K.append(bh["constant_K"])
         for l in range(nlev):  # :154-160
-            _coefs(psi[l], phi[l], a[l], rhs[l], bh)
+            _coefs(psi[l], phi[l], a[l], rhs[l], bh, punct)
         amr = AMRSolver(list(zip(grids, a, b)), op_params, sp)  # :163-170
         solver = BiCGStabSolver(MultilevelLinearOp(amr, prm.numMGIterations),
                                 tolerance=prm.tolerance, max_iterations=prm.max_iterations,
                                 norm_type=0)
         if output_dir is not None:  # :180-181
             output_solver_data(dpsi, rhs, psi, bh, it, refs,
-                               os.path.join(output_dir, f"vcPoissonOut.3d_{it}.hdf5"), phi=phis)
+                               os.path.join(output_dir, f"vcPoissonOut.3d_{it}.hdf5"), phi=phis,
+                               punctures=punct)
         res.linear_iterations.append(solver.solve(dpsi, rhs))  # :184
         for l in range(nlev):  # :189-205
             if l > 0:
@@ -244,7 +258,8 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
     if output_dir is not None:  # :227-230
         def write():
             output_final_data(psi, bh, nlev - 1, refs,
-                              os.path.join(output_dir, "vcPoissonFinal.3d.hdf5"), phi=phis)
+                              os.path.join(output_dir, "vcPoissonFinal.3d.hdf5"), phi=phis,
+                              punctures=punct)
     return finish_nl_loop(res, write)
 
 

@@ -12,7 +12,9 @@ A_ij_0 are not stored fields here: set_initial_conditions sets them
 analytically and nothing changes them, so the kernels evaluate them in place.
 phi_0 is evaluated in place too (the Gaussian of MyPhiFunction.H) unless the
 caller passes the stored field (`phi`, one LevelData per level; phi.py): then
-the "phi" / "phi_0" component is copied from it.
+the "phi" / "phi_0" component is copied from it.  With `punctures` (a
+punctures.PunctureSet) the A_ij_0, A_ij and chi components come from the
+puncture table instead of the deck's two holes.
 """
 from __future__ import annotations
 
@@ -23,6 +25,7 @@ import numpy as np
 
 from ._lib import call, io_call
 from .core import BH_KEYS, LevelData
+from .punctures import table_args
 
 GRCHOMBO_VARS = (  # GRChomboUserVariables.hpp:58-75
     "chi", "h11", "h12", "h13", "h22", "h23", "h33", "K", "A11", "A12", "A13", "A22", "A23",
@@ -47,12 +50,18 @@ def _enc(filename: Optional[str]):
 def output_final_data(psi: Sequence[LevelData], bh: dict, max_level: int = 0,
                       ref_ratio: Optional[Sequence[int]] = None,
                       filename: Optional[str] = None,
-                      phi: Optional[Sequence[LevelData]] = None) -> None:
+                      phi: Optional[Sequence[LevelData]] = None, punctures=None) -> None:
     """output_final_data (WriteOutput.H:127-227); constant_K = bh['constant_K'].
     filename None: "vcPoissonFinal.3d.hdf5" in the working directory.
-    phi: the stored phi_0 per level (None: the analytic Gaussian)."""
+    phi: the stored phi_0 per level (None: the analytic Gaussian).
+    punctures: the puncture table (None: the deck's two holes)."""
     n = len(psi)
     rr = list(ref_ratio) if ref_ratio is not None else [2] * n
+    if punctures is not None:
+        io_call("mgic_io_write_final_data_punct", _enc(filename), n, _handles(psi),
+                _handles(phi) if phi is not None else None, _bh(bh), *table_args(punctures),
+                int(max_level), (ctypes.c_int * n)(*rr))
+        return
     if phi is not None:
         io_call("mgic_io_write_final_data_phi", _enc(filename), n, _handles(psi), _handles(phi),
                 _bh(bh), int(max_level), (ctypes.c_int * n)(*rr))
@@ -65,12 +74,18 @@ def output_solver_data(dpsi: Sequence[LevelData], rhs: Sequence[LevelData],
                        psi: Sequence[LevelData], bh: dict, iteration: int,
                        ref_ratio: Optional[Sequence[int]] = None,
                        filename: Optional[str] = None,
-                       phi: Optional[Sequence[LevelData]] = None) -> None:
+                       phi: Optional[Sequence[LevelData]] = None, punctures=None) -> None:
     """output_solver_data (WriteOutput.H:52-123) for NL iteration `iteration`.
     filename None: "vcPoissonOut.3d_<iteration>.hdf5".
-    phi: the stored phi_0 per level (None: the analytic Gaussian)."""
+    phi: the stored phi_0 per level (None: the analytic Gaussian).
+    punctures: the puncture table (None: the deck's two holes)."""
     n = len(psi)
     rr = list(ref_ratio) if ref_ratio is not None else [2] * n
+    if punctures is not None:
+        io_call("mgic_io_write_solver_data_punct", _enc(filename), n, _handles(dpsi),
+                _handles(rhs), _handles(psi), _handles(phi) if phi is not None else None,
+                _bh(bh), *table_args(punctures), (ctypes.c_int * n)(*rr), int(iteration))
+        return
     if phi is not None:
         io_call("mgic_io_write_solver_data_phi", _enc(filename), n, _handles(dpsi), _handles(rhs),
                 _handles(psi), _handles(phi), _bh(bh), (ctypes.c_int * n)(*rr), int(iteration))
@@ -81,21 +96,22 @@ def output_solver_data(dpsi: Sequence[LevelData], rhs: Sequence[LevelData],
 
 def grchombo_vars(psi: LevelData, n: int, bh: dict, k0: int = 0, nk: Optional[int] = None,
                   out_device_ptr: Optional[int] = None,
-                  phi: Optional[LevelData] = None) -> Optional[np.ndarray]:
+                  phi: Optional[LevelData] = None, punctures=None) -> Optional[np.ndarray]:
     """set_output_data for local box n, planes [k0, k0+nk): (31, nk, ny, nx) on
     the host, or written to device memory at out_device_ptr (returns None).
-    phi: the stored phi_0 (None: the analytic Gaussian)."""
-    return _vars(0, psi, None, None, n, bh, k0, nk, out_device_ptr, phi)
+    phi: the stored phi_0 (None: the analytic Gaussian).
+    punctures: the puncture table (None: the deck's two holes)."""
+    return _vars(0, psi, None, None, n, bh, k0, nk, out_device_ptr, phi, punctures)
 
 
 def solver_vars(dpsi: LevelData, rhs: LevelData, psi: LevelData, n: int, bh: dict, k0: int = 0,
                 nk: Optional[int] = None, out_device_ptr: Optional[int] = None,
-                phi: Optional[LevelData] = None):
+                phi: Optional[LevelData] = None, punctures=None):
     """output_solver_data's 10 components for local box n: (10, nk, ny, nx)."""
-    return _vars(1, psi, dpsi, rhs, n, bh, k0, nk, out_device_ptr, phi)
+    return _vars(1, psi, dpsi, rhs, n, bh, k0, nk, out_device_ptr, phi, punctures)
 
 
-def _vars(kind, psi, dpsi, rhs, n, bh, k0, nk, dev, phi=None):
+def _vars(kind, psi, dpsi, rhs, n, bh, k0, nk, dev, phi=None, punctures=None):
     lo, hi = psi.grid.local_box(n)[:3], psi.grid.local_box(n)[3:]
     nx, ny, nz = (hi[d] - lo[d] + 1 for d in range(3))
     nk = nz - k0 if nk is None else nk
@@ -105,7 +121,14 @@ def _vars(kind, psi, dpsi, rhs, n, bh, k0, nk, dev, phi=None):
     else:
         out = np.empty((nc, nk, ny, nx))
         ptr = out.ctypes.data_as(ctypes.c_void_p)
-    if phi is not None and kind == 0:
+    hphi = phi.handle if phi is not None else None
+    if punctures is not None and kind == 0:
+        call("mgic_field_grchombo_vars_punct", psi.handle, hphi, n, k0, nk, _bh(bh),
+             *table_args(punctures), ptr, int(dev is not None))
+    elif punctures is not None:
+        call("mgic_field_solver_vars_punct", dpsi.handle, rhs.handle, psi.handle, hphi, n, k0, nk,
+             _bh(bh), *table_args(punctures), ptr, int(dev is not None))
+    elif phi is not None and kind == 0:
         call("mgic_field_grchombo_vars_phi", psi.handle, phi.handle, n, k0, nk, _bh(bh), ptr,
              int(dev is not None))
     elif phi is not None:

@@ -61,6 +61,9 @@ class PoissonParameters:
     bh2_offset: float = 0.0
     bh1_momentum: float = 0.0
     bh2_momentum: float = 0.0
+    # the optional puncture table (num_punctures, puncture1 .. punctureN): rows
+    # of m x y z Px Py Pz Jx Jy Jz (punctures.py); None: the two holes above
+    punctures: Optional[list] = None
 
     def bh(self, constant_K: float = 0.0) -> dict:
         """Inputs of set_a_coef / set_rhs (domain length of direction 0)."""
@@ -126,6 +129,19 @@ def read_params(text: str, overrides: Optional[Dict[str, str]] = None) -> Poisso
         val = get(k, conv, required=False)
         if val is not None:
             setattr(p, k, val)
+    # the puncture table (not a key of the reference): absent = nothing changes
+    npunct = get("num_punctures", int, required=False)
+    if npunct is not None:
+        rows = []
+        for i in range(1, npunct + 1):
+            key = f"puncture{i}"
+            if key not in kv:
+                raise KeyError(f"ParmParse::get: key '{key}' not found")
+            if len(kv[key]) != 10:
+                raise ValueError(f"{key} needs ten numbers (m x y z Px Py Pz Jx Jy Jz), "
+                                 f"got {len(kv[key])}")
+            rows.append([float(x) for x in kv[key]])
+        p.punctures = rows
     return p
 
 
