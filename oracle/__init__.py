@@ -3,8 +3,11 @@
 A ctypes binding of oracle/liboracle.so (plain C restatement of the
 reference path, see mgic_oracle.h).  Only tests/, __graft_entry__.smoke()
 and bench.py's cpu_baseline leg import this package, and only as the
-checker.  Parity status: "parity unpinned" (see mgic_oracle.h header and
-DESIGN.md).
+checker.  Parity status (mgic_oracle.h header): the ChF kernels
+and the SetLevelData.cpp functions are pinned bit for bit to the compiled
+reference (oracle/reference.py, tests/test_reference_parity.py); the operator's
+C++, the boundary conditions, the tagging and everything restated from Chombo
+remain "parity unpinned".
 
 Arrays are numpy float64 of shape (nz, ny, nx) (i fastest in memory) over
 an explicit box; `Fab(arr, lo)` ties an array to its box's low corner.
@@ -63,6 +66,7 @@ _sig = {
     "orc_vccomputeop3d": [PF, PF, c_double, PF, c_double, PF, PI, PI, c_double],
     "orc_vccomputeres3d": [PF, PF, PF, c_double, PF, c_double, PF, PI, PI, c_double],
     "orc_restrictresvc3d": [PF, PF, PF, c_double, PF, c_double, PF, PI, PI, c_double],
+    "orc_restrictresvc3d_acc": [PF, PF, PF, c_double, PF, c_double, PF, PI, PI, c_double],
     "orc_lambda": [PF, PF, PI, PI, c_double, c_double, c_double],
     "orc_average": [PF, PF, PI, PI, c_int, c_int],
     "orc_prolong": [PF, PF, PI, PI, PI, PI, PI, PI, c_int],
@@ -162,8 +166,12 @@ def residual(res: Fab, u: Fab, rhs: Fab, alpha, a: Fab, beta, b: Fab, rlo, rhi, 
     _lib.orc_vccomputeres3d(res.c, u.c, rhs.c, alpha, a.c, beta, b.c, _i3(rlo), _i3(rhi), dx)
 
 
-def restrict_residual(res: Fab, u: Fab, rhs: Fab, alpha, a: Fab, beta, b: Fab, rlo, rhi, dx):
-    _lib.orc_restrictresvc3d(res.c, u.c, rhs.c, alpha, a.c, beta, b.c, _i3(rlo), _i3(rhi), dx)
+def restrict_residual(res: Fab, u: Fab, rhs: Fab, alpha, a: Fab, beta, b: Fab, rlo, rhi, dx,
+                      accumulate=False):
+    """restrictResidual for one box (res zeroed first); accumulate: the
+    Fortran RESTRICTRESVC3D alone, which adds to what res holds."""
+    f = _lib.orc_restrictresvc3d_acc if accumulate else _lib.orc_restrictresvc3d
+    f(res.c, u.c, rhs.c, alpha, a.c, beta, b.c, _i3(rlo), _i3(rhi), dx)
 
 
 def lam(out: Fab, a: Fab, rlo, rhi, alpha, beta, dx):

@@ -2,10 +2,13 @@
  * mgic_oracle.c -- CPU restatement of the reference multigrid hot path.
  *
  * TEST INFRASTRUCTURE ONLY (see mgic_oracle.h): the checker for tests/,
- * __graft_entry__.smoke() and bench.py's cpu_baseline leg.  Parity status:
- * "parity unpinned" (the ChomboFortran reference cannot be built here and
- * ships no golden vectors); every formula below cites the reference line it
- * restates, and [Chombo] marks semantics restated from Chombo 3.2.
+ * __graft_entry__.smoke() and bench.py's cpu_baseline leg.  Parity status
+ * (mgic_oracle.h has the list): the ChF kernels and the SetLevelData.cpp
+ * functions are pinned bit for bit to the compiled reference
+ * (tests/test_reference_parity.py); the C++ of VariableCoeffPoissonOperator
+ * .cpp, SetBCs.cpp, SetGrids.cpp, and everything marked [Chombo] (restated
+ * from Chombo 3.2) remain "parity unpinned".  Every formula below cites the
+ * reference line it restates.
  *
  * Floating point: compiled with -ffp-contract=off; every expression keeps
  * the reference's evaluation order (Fortran/C++ left-to-right, parentheses
@@ -122,10 +125,18 @@ void orc_restrictresvc3d(orc_fab *res, const orc_fab *dpsi, const orc_fab *rhs,
                          double alpha, const orc_fab *aCoef, double beta,
                          const orc_fab *bCoef, const int *rlo, const int *rhi,
                          double dx) {
-  const double dxinv = 1.0 / (dx * dx); /* :401 */
-  const double denom = 2 * 2 * 2;       /* :402 D_TERM(2, *2, *2) */
   const size_t ntot = fab_nx(res) * fab_ny(res) * fab_nz(res);
   for (size_t n = 0; n < ntot; ++n) res->p[n] = 0.0; /* res.setVal(0.0) */
+  orc_restrictresvc3d_acc(res, dpsi, rhs, alpha, aCoef, beta, bCoef, rlo, rhi, dx);
+}
+
+/* RESTRICTRESVC3D alone, as the Fortran has it: accumulates into res */
+void orc_restrictresvc3d_acc(orc_fab *res, const orc_fab *dpsi, const orc_fab *rhs,
+                             double alpha, const orc_fab *aCoef, double beta,
+                             const orc_fab *bCoef, const int *rlo, const int *rhi,
+                             double dx) {
+  const double dxinv = 1.0 / (dx * dx); /* :401 */
+  const double denom = 2 * 2 * 2;       /* :402 D_TERM(2, *2, *2) */
   int civ[3];
   for (int d = 0; d < 3; ++d) civ[d] = floordiv2(rlo[d]); /* coarsen(iv, 2) */
   const int kc_lo = civ[2], kc_hi = civ[2] + (rhi[2] - rlo[2]) / 2;

@@ -4,14 +4,25 @@
  * __graft_entry__.smoke() and by bench.py's cpu_baseline leg, as the checker.
  * It is never linked into, loaded by, or called from the product library.
  *
- * PARITY STATUS: "parity unpinned" against the reference binary.  The
- * reference kernels are ChomboFortran (.ChF) that need Chombo's chfpp
- * preprocessor and Chombo 3.2 libraries, neither of which exists in this
- * image, and the reference ships no tests, fixtures or golden vectors
- * (SURVEY.md §4.1, §8(c)).  This file restates the arithmetic from the
- * reference text, statement by statement, citing file:line.  Behaviour that
- * lives in Chombo (BC fill, exchange, prolongation, V-cycle, BiCGStab) is
- * restated from Chombo 3.2's published algorithm and marked [Chombo].
+ * PARITY STATUS.  This file restates the arithmetic from the reference
+ * text, statement by statement, citing file:line.
+ *   PINNED to compiled reference code, bit for bit
+ *   (tests/test_reference_parity.py against oracle/_ref/libmgic_ref.so, which
+ *   oracle/ref/ compiles from a checkout of the reference; the recorded
+ *   outputs in tests/golden/reference_kernels.npz where there is none): the
+ *   ChomboFortran subroutines of VariableCoeffPoissonOperatorF.ChF and
+ *   SetLevelDataF.ChF (the four orc_*3d kernels, orc_getlaplacianpsif and its
+ *   gradient form) and Source/SetLevelData.cpp with SetBinaryBH.H and
+ *   MyPhiFunction.H (orc_nl_coefs, orc_nl_integrand, orc_binary_bh_coefs,
+ *   orc_output_vars).
+ *   STILL A RESTATEMENT ("parity unpinned"): the C++ of
+ *   VariableCoeffPoissonOperator.cpp (levelGSRB's pass order, resetLambda,
+ *   restrictResidual's setVal(0), prolongIncrement), SetBCs.cpp, SetGrids.cpp's
+ *   tagging, PoissonParameters.cpp, WriteOutput.H's file layout, and
+ *   everything that lives in Chombo and not in the reference tree (BC fill,
+ *   exchange, prolongation, V-cycle, BiCGStab: restated from Chombo 3.2's
+ *   published algorithm and marked [Chombo]).  The reference ships no tests,
+ *   fixtures or golden vectors for those.
  *
  * Layout: a "fab" is one component over an inclusive cell box [lo,hi]
  * (ghost cells included), column-major with i fastest -- the same layout as
@@ -51,6 +62,11 @@ void orc_restrictresvc3d(orc_fab *res, const orc_fab *dpsi, const orc_fab *rhs,
                          double alpha, const orc_fab *aCoef, double beta,
                          const orc_fab *bCoef, const int *rlo, const int *rhi,
                          double dx);
+/* the Fortran subroutine alone: no setVal(0), it accumulates into res */
+void orc_restrictresvc3d_acc(orc_fab *res, const orc_fab *dpsi, const orc_fab *rhs,
+                             double alpha, const orc_fab *aCoef, double beta,
+                             const orc_fab *bCoef, const int *rlo, const int *rhi,
+                             double dx);
 
 /* ---- operator helpers ---- */
 void orc_lambda(orc_fab *lam, const orc_fab *aCoef, const int *rlo,

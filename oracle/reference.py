@@ -1,0 +1,318 @@
+"""The compiled reference -- TEST INFRASTRUCTURE ONLY.
+
+A ctypes binding of oracle/_ref/libmgic_ref.so, which oracle/ref/Makefile
+compiles from a checkout of the reference itself: the seven ChomboFortran
+subroutines (translated by oracle/ref/chf2f.py, compiled by flang) and
+Source/SetLevelData.cpp with its headers (compiled unmodified against
+oracle/ref/chombo_standin.H).  This is what the oracle's restatement is
+pinned to; nothing here restates arithmetic.
+
+Array conventions are those of oracle/__init__.py: numpy float64 of shape
+(nz, ny, nx) over an explicit box (i fastest), `Fab(arr, lo)` ties an array
+to its box's low corner.  A 4-D array (ncomp, nz, ny, nx) is a FArrayBox of
+ncomp components.
+
+The library is never built on import.  `build()` compiles it when the
+reference checkout is there; `available()` says whether it can be loaded.
+The checkout is looked for in the directory `reference` beside the
+repository, or where the environment variable MGIC_REFERENCE_DIR points.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+import subprocess
+import sys
+from ctypes import POINTER, byref, c_double, c_int
+from typing import Sequence
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIB = os.path.join(HERE, "_ref", "libmgic_ref.so")
+RECIPE = os.path.join(HERE, "ref")
+
+# component order of the reference's two variable enums
+MULTIGRID_VARS = ("psi", "A11_0", "A12_0", "A13_0", "A22_0", "A23_0", "A33_0", "phi_0")
+GRCHOMBO_VARS = ("chi", "h11", "h12", "h13", "h22", "h23", "h33", "K", "A11", "A12", "A13", "A22",
+                 "A23", "A33", "Theta", "Gamma1", "Gamma2", "Gamma3", "lapse", "shift1", "shift2",
+                 "shift3", "B1", "B2", "B3", "phi", "Pi", "Ham", "Mom1", "Mom2", "Mom3")
+C_PSI, C_PHI_0 = 0, 7
+
+
+def reference_dir() -> str:
+    """Where the reference checkout is expected (it need not exist)."""
+    return os.environ.get("MGIC_REFERENCE_DIR") or os.path.join(
+        os.path.dirname(os.path.dirname(HERE)), "reference")
+
+
+def checkout_present() -> bool:
+    return os.path.isfile(os.path.join(reference_dir(), "Source", "SetLevelData.cpp"))
+
+
+def available() -> bool:
+    return os.path.isfile(LIB)
+
+
+def build() -> bool:
+    """Compile the library when the checkout is present (an error if that
+    fails); leave whatever oracle/_ref/ holds alone when it is not."""
+    if not checkout_present():
+        return available()
+    subprocess.run(["make", "-s", "-C", RECIPE, "REF=" + os.path.abspath(reference_dir()),
+                    "PYTHON=" + (sys.executable or "python3")], check=True)
+    return True
+
+
+class _CFab(ctypes.Structure):
+    _fields_ = [("p", POINTER(c_double)), ("lo", c_int * 3), ("hi", c_int * 3), ("ncomp", c_int)]
+
+
+class _Params(ctypes.Structure):
+    _fields_ = [("L", c_double * 3)] + [(k, c_double) for k in (
+        "G_Newton", "phi_amplitude", "phi_wavelength", "bh1_bare_mass", "bh2_bare_mass",
+        "bh1_spin", "bh2_spin", "bh1_momentum", "bh2_momentum", "bh1_offset", "bh2_offset")]
+
+
+_lib = None
+PD, PI, PF, PP = POINTER(c_double), POINTER(c_int), POINTER(_CFab), POINTER(_Params)
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        if not available():
+            raise FileNotFoundError(LIB + ": build it with oracle.reference.build()")
+        L = ctypes.CDLL(LIB)
+        for name, args, res in (
+                ("mgic_ref_mayday_count", [], c_int),
+                ("mgic_ref_mayday_reset", [], None),
+                ("mgic_ref_set_initial_conditions", [PP, PF, PF, c_double], None),
+                ("mgic_ref_set_rhs", [PP, PF, PF, c_double, c_double], None),
+                ("mgic_ref_set_a_coef", [PP, PF, PF, c_double, c_double], None),
+                ("mgic_ref_set_b_coef", [PP, PF, c_double], None),
+                ("mgic_ref_set_constant_K_integrand", [PP, PF, PF, c_double], None),
+                ("mgic_ref_set_regrid_condition", [PP, PF, PF, c_double], None),
+                ("mgic_ref_set_update_psi0", [PF, PF], None),
+                ("mgic_ref_set_output_data", [PP, PF, PF, c_double, c_double], None),
+                ("mgic_ref_set_m_value", [PP, c_double, c_double], c_double),
+                ("mgic_ref_get_Aij", [PP, c_int, c_int, c_double, c_double] + [PD] * 6, c_double),
+                ("mgic_ref_set_binary_bh_Aij", [PP, PF, PI, PD], None),
+                ("mgic_ref_set_binary_bh_psi", [PP, PD], c_double),
+                ("mgic_ref_my_phi_function", [PD, c_double, c_double, PD], c_double),
+                ("mgic_ref_num_multigrid_vars", [], c_int),
+                ("mgic_ref_num_grchombo_vars", [], c_int)):
+            f = getattr(L, name)
+            f.argtypes, f.restype = args, res
+        for name in ("gsrbhelmholtzvc3d_", "vccomputeop3d_", "vccomputeres3d_", "restrictresvc3d_",
+                     "sumfaces_", "getlaplacianpsif_", "getrhogradphif_"):
+            getattr(L, name).restype = None
+        assert L.mgic_ref_num_multigrid_vars() == len(MULTIGRID_VARS)
+        assert L.mgic_ref_num_grchombo_vars() == len(GRCHOMBO_VARS)
+        _lib = L
+    return _lib
+
+
+def mayday_count() -> int:
+    """MAYDAYERROR / CH_assert calls recorded since the last reset."""
+    return lib().mgic_ref_mayday_count()
+
+
+def mayday_reset() -> None:
+    lib().mgic_ref_mayday_reset()
+
+
+class Fab:
+    """numpy array (nz, ny, nx) or (ncomp, nz, ny, nx) over the box at `lo`."""
+
+    def __init__(self, arr: np.ndarray, lo: Sequence[int]):
+        assert arr.dtype == np.float64 and arr.flags.c_contiguous and arr.ndim in (3, 4)
+        self.arr = arr
+        self.ncomp = arr.shape[0] if arr.ndim == 4 else 1
+        self.lo = tuple(int(x) for x in lo)
+        nz, ny, nx = arr.shape[-3:]
+        self.hi = (self.lo[0] + nx - 1, self.lo[1] + ny - 1, self.lo[2] + nz - 1)
+        self._c = _CFab(arr.ctypes.data_as(PD), (c_int * 3)(*self.lo), (c_int * 3)(*self.hi),
+                        self.ncomp)
+
+    @property
+    def c(self):
+        return byref(self._c)
+
+    def fra1(self):
+        """CHF_FRA1: pointer, lo0..2, hi0..2 (all by reference)."""
+        return [self.arr.ctypes.data_as(PD)] + _ints(self.lo) + _ints(self.hi)
+
+    def fra(self):
+        """CHF_FRA: CHF_FRA1 then the number of components."""
+        return self.fra1() + _ints([self.ncomp])
+
+
+def _ints(v):
+    return [byref(c_int(int(x))) for x in v]
+
+
+def _real(x):
+    return byref(c_double(float(x)))
+
+
+# ---------------------------------------------------------------- the .ChF kernels
+# `abi`: another library that exports the same symbols with the same argument
+# lists (the HIP drop-ins of include/mgic_chf.h); None: the compiled reference.
+def gsrb(u: Fab, rhs: Fab, rlo, rhi, dx, alpha, a: Fab, beta, b: Fab, lam: Fab, red_black: int,
+         abi=None):
+    (abi or lib()).gsrbhelmholtzvc3d_(*u.fra(), *rhs.fra(), *_ints(rlo), *_ints(rhi), _real(dx),
+                             _real(alpha), *a.fra(), _real(beta), *b.fra(), *lam.fra(),
+                             *_ints([red_black]))
+
+
+def apply_op(lof: Fab, u: Fab, alpha, a: Fab, beta, b: Fab, rlo, rhi, dx, abi=None):
+    (abi or lib()).vccomputeop3d_(*lof.fra(), *u.fra(), _real(alpha), *a.fra(), _real(beta), *b.fra(),
+                         *_ints(rlo), *_ints(rhi), _real(dx))
+
+
+def residual(res: Fab, u: Fab, rhs: Fab, alpha, a: Fab, beta, b: Fab, rlo, rhi, dx, abi=None):
+    (abi or lib()).vccomputeres3d_(*res.fra(), *u.fra(), *rhs.fra(), _real(alpha), *a.fra(), _real(beta),
+                          *b.fra(), *_ints(rlo), *_ints(rhi), _real(dx))
+
+
+def restrict_residual(res: Fab, u: Fab, rhs: Fab, alpha, a: Fab, beta, b: Fab, rlo, rhi, dx,
+                      abi=None):
+    """RESTRICTRESVC3D as the Fortran has it: ACCUMULATES into res(i/2, j/2, k/2)."""
+    (abi or lib()).restrictresvc3d_(*res.fra(), *u.fra(), *rhs.fra(), _real(alpha), *a.fra(), _real(beta),
+                           *b.fra(), *_ints(rlo), *_ints(rhi), _real(dx))
+
+
+def sumfaces(lhs: Fab, beta, b: Fab, lo, hi, direction: int, scale):
+    lib().sumfaces_(*lhs.fra(), _real(beta), *b.fra(), *_ints(lo), *_ints(hi),
+                    *_ints([direction]), _real(scale))
+
+
+def laplacian_psi(out: Fab, psi: Fab, dx, lo, hi, abi=None):
+    (abi or lib()).getlaplacianpsif_(*out.fra1(), *psi.fra1(), _real(dx), *_ints(lo), *_ints(hi))
+
+
+def rho_grad_phi(out: Fab, phi: Fab, dx, lo, hi, abi=None):
+    (abi or lib()).getrhogradphif_(*out.fra1(), *phi.fra1(), _real(dx), *_ints(lo), *_ints(hi))
+
+
+def _shape(lo, hi, grow=0):
+    return tuple(hi[d] - lo[d] + 1 + 2 * grow for d in (2, 1, 0))
+
+
+def getlaplacianpsif(psi_g, lo, hi, dx):
+    """GETLAPLACIANPSIF over [lo, hi]; psi_g over the box grown by one."""
+    out = np.zeros(_shape(lo, hi))
+    laplacian_psi(Fab(out, lo), Fab(np.ascontiguousarray(psi_g), [l - 1 for l in lo]), dx, lo, hi)
+    return out
+
+
+def getrhogradphif(phi_g, lo, hi, dx):
+    """GETRHOGRADPHIF over [lo, hi]; phi_g over the box grown by one."""
+    out = np.zeros(_shape(lo, hi))
+    rho_grad_phi(Fab(out, lo), Fab(np.ascontiguousarray(phi_g), [l - 1 for l in lo]), dx, lo, hi)
+    return out
+
+
+# ---------------------------------------------------------------- SetLevelData.cpp
+def _params(bh: dict) -> _Params:
+    L = bh["domain_length"]
+    L = (L, L, L) if np.isscalar(L) else tuple(L)
+    return _Params((c_double * 3)(*L), *[bh[k] for k in (
+        "G_Newton", "phi_amplitude", "phi_wavelength", "bh1_bare_mass", "bh2_bare_mass",
+        "bh1_spin", "bh2_spin", "bh1_momentum", "bh2_momentum", "bh1_offset", "bh2_offset")])
+
+
+def initial_conditions(bh: dict, lo, hi, dx):
+    """set_initial_conditions over [lo, hi]: (multigrid_vars (8, nz, ny, nx)
+    in MULTIGRID_VARS order, dpsi)."""
+    mv = np.full((len(MULTIGRID_VARS),) + _shape(lo, hi), np.nan)
+    dpsi = np.full(_shape(lo, hi), np.nan)
+    p = _params(bh)
+    lib().mgic_ref_set_initial_conditions(byref(p), Fab(mv, lo).c, Fab(dpsi, lo).c, float(dx))
+    return mv, dpsi
+
+
+def multigrid_vars(bh: dict, lo, hi, dx, psi=None, grow=1):
+    """The reference's multigrid_vars over [lo, hi] grown by `grow`, as
+    set_initial_conditions leaves them, with psi replaced when given."""
+    glo, ghi = [l - grow for l in lo], [h + grow for h in hi]
+    mv, _ = initial_conditions(bh, glo, ghi, dx)
+    if psi is not None:
+        assert np.shape(psi) == mv.shape[1:]
+        mv[C_PSI] = psi
+    return mv, glo
+
+
+def _level(fn, bh, lo, hi, dx, psi, *tail, ncomp=1, grow=1):
+    mv, glo = multigrid_vars(bh, lo, hi, dx, psi, grow)
+    out = np.full(((ncomp,) if ncomp > 1 else ()) + _shape(lo, hi), np.nan)
+    p = _params(bh)
+    fn(byref(p), Fab(out, lo).c, Fab(mv, glo).c, float(dx), *tail)
+    return out
+
+
+def nl_coefs(bh: dict, lo, hi, dx, psi=None):
+    """set_a_coef, set_rhs at psi given over [lo-1, hi+1] (None: psi = 1)."""
+    K = float(bh["constant_K"])
+    return (_level(lib().mgic_ref_set_a_coef, bh, lo, hi, dx, psi, K),
+            _level(lib().mgic_ref_set_rhs, bh, lo, hi, dx, psi, K))
+
+
+def nl_integrand(bh: dict, lo, hi, dx, psi=None):
+    """set_constant_K_integrand at psi over [lo-1, hi+1]."""
+    return _level(lib().mgic_ref_set_constant_K_integrand, bh, lo, hi, dx, psi)
+
+
+def regrid_condition(bh: dict, lo, hi, dx, psi=None):
+    """set_regrid_condition at psi over [lo-1, hi+1]."""
+    return _level(lib().mgic_ref_set_regrid_condition, bh, lo, hi, dx, psi)
+
+
+def output_vars(bh: dict, lo, hi, dx, psi):
+    """set_output_data: the 31 GRChombo variables (31, nz, ny, nx) from psi
+    over [lo, hi] (constant_K from bh)."""
+    return _level(lib().mgic_ref_set_output_data, bh, lo, hi, dx, psi, float(bh["constant_K"]),
+                  ncomp=len(GRCHOMBO_VARS), grow=0)
+
+
+def update_psi0(mv: np.ndarray, mlo, dpsi: np.ndarray, dlo):
+    lib().mgic_ref_set_update_psi0(Fab(mv, mlo).c, Fab(dpsi, dlo).c)
+
+
+def m_value(bh: dict, phi_here: float, constant_K: float) -> float:
+    p = _params(bh)
+    return lib().mgic_ref_set_m_value(byref(p), float(phi_here), float(constant_K))
+
+
+def _v3(v):
+    return (c_double * 3)(*[float(x) for x in v])
+
+
+def get_Aij(bh: dict, i, j, r1, r2, n1, n2, J1, J2, P1, P2) -> float:
+    p = _params(bh)
+    return lib().mgic_ref_get_Aij(byref(p), int(i), int(j), float(r1), float(r2), _v3(n1), _v3(n2),
+                                  _v3(J1), _v3(J2), _v3(P1), _v3(P2))
+
+
+def binary_bh_psi(bh: dict, loc) -> float:
+    p = _params(bh)
+    return lib().mgic_ref_set_binary_bh_psi(byref(p), _v3(loc))
+
+
+def binary_bh_psi_on_box(bh: dict, lo, hi, dx):
+    """set_binary_bh_psi at every cell centre of [lo, hi], the location
+    computed as SetLevelData.cpp computes it."""
+    L = bh["domain_length"]
+    out = np.empty(_shape(lo, hi))
+    for k in range(lo[2], hi[2] + 1):
+        for j in range(lo[1], hi[1] + 1):
+            for i in range(lo[0], hi[0] + 1):
+                loc = [(float(v) + 0.5) * dx - L / 2.0 for v in (i, j, k)]
+                out[k - lo[2], j - lo[1], i - lo[0]] = binary_bh_psi(bh, loc)
+    return out
+
+
+def my_phi_function(loc, amplitude, wavelength, L) -> float:
+    L = (L, L, L) if np.isscalar(L) else L
+    return lib().mgic_ref_my_phi_function(_v3(loc), float(amplitude), float(wavelength), _v3(L))

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Regenerate the committed fixtures in tests/golden/ from the CPU oracle.
 
-The reference has no tests or vectors and cannot be built here (DESIGN.md
-§4), so these fixtures are REGRESSION vectors of the oracle restatement
-(SURVEY.md §8(c) "fixtures to commit"), not pins against the reference:
+The first three are REGRESSION vectors of the oracle restatement (SURVEY.md
+§8(c) "fixtures to commit"); since the oracle's kernels and level-data
+functions are pinned bit for bit to the compiled reference
+(tests/test_reference_parity.py), they are the reference's values too:
 
   kernels12.npz   12^3 box (+1 ghost), seed 20261015: inputs u, rhs, a, b;
                   outputs of GSRB pass 0, then pass 1 (one sweep), OP, RES,
@@ -16,6 +17,17 @@ The reference has no tests or vectors and cannot be built here (DESIGN.md
                   each of 4 AMRMultiGrid iterations, plus the final phi.
   binary_bh64.json  params.txt's 64^3 SetBinaryBH aCoef / rhs at 64 sampled
                   cells (float.hex), psi = 1.
+
+The fourth is written by the COMPILED reference (oracle/reference.py, which
+needs a checkout of the reference and flang) and is skipped, with a notice,
+where that library is not built:
+
+  reference_kernels.npz  inputs and the outputs the reference's own Fortran
+                  and SetLevelData.cpp wrote, for the cases
+                  tests/reference_cases.py names: every ChF kernel on an
+                  8x6x4 box and on the special-value case (-0.0, subnormal,
+                  1e300, Inf, NaN), every level-data function on a 6^3 part
+                  of the 16^3 lattice for params.txt's deck and a second one.
 
 usage: python tests/golden/make_golden.py
 """
@@ -108,8 +120,20 @@ def binary_bh64():
         json.dump(data, f, indent=0)
 
 
+def reference_kernels():
+    from oracle import reference
+    from tests import reference_cases
+    if not reference.build():
+        print("reference_kernels.npz NOT regenerated: no reference checkout at",
+              reference.reference_dir(), "and no", reference.LIB)
+        return
+    np.savez_compressed(reference_cases.FIXTURE, **reference_cases.build_fixture())
+    assert reference.mayday_count() == 0
+
+
 if __name__ == "__main__":
     kernels12()
     vcycle16()
     binary_bh64()
+    reference_kernels()
     print("fixtures written to", HERE)

@@ -4,8 +4,11 @@ CPU: the oracle still reproduces every fixture bit for bit (regression of
 the checker itself).  GPU: the HIP path reproduces the same fixtures through
 the C ABI -- the ChF drop-ins on the 12^3 kernel vectors, the operator-level
 V-cycle on the 16^3 hierarchy -- bit for bit, without consulting the oracle.
-Parity status of the fixtures: regression vectors of the restatement
-("parity unpinned").
+Parity status of these fixtures: regression vectors of the restatement.  Its
+ChF kernels are pinned to the compiled reference by
+tests/test_reference_parity.py (whose own fixture, reference_kernels.npz, the
+compiled reference wrote); lambda, the averages and the V-cycle are still
+"parity unpinned" (DESIGN.md §4).
 """
 import ctypes
 import json
