@@ -518,6 +518,45 @@ MGIC_API int mgic_field_solver_vars_punct(mgic_field dpsi, mgic_field rhs, mgic_
                                           mgic_field phi, int n, int k0, int nk,
                                           const double bh[13], int npunct, const double *table,
                                           double *out, int out_on_device);
+/* ---- Matter: the scalar field's kinetic and potential energy.  set_m_value
+ * (SetLevelData.cpp:266-278) reads rho = 0.5 * Pi_field * Pi_field + V_of_phi
+ * with both set to 0.0 and a note that V(phi) and Pi may be added later; the
+ * entry points above keep those zeros.  The *_matter entry points fill the
+ * slot:
+ *   V(phi) = V0 + 0.5 * mass * mass * phi * phi
+ *               + 0.25 * lambda * phi * phi * phi * phi   (left to right),
+ *   rho = 0.5 * Pi * Pi + V(phi_0),
+ * phi_0 the cell's scalar field (the stored phi if given, else the Gaussian)
+ * and Pi the cell's value of the stored field pi.  m = (2/3) K^2 - 16 pi G rho
+ * and every expression that uses it are as written in the reference, so rho
+ * has the psi weighting the reference's slot gives it; K is constant_K for
+ * the coefficients and 0 for the integrand and the regrid condition.
+ *
+ * pot[3] = V0, mass, lambda.  pi: one value per cell on the layout of the
+ * other fields (only valid cells are read; it is never differenced), or NULL
+ * for Pi = 0.  Only Pi * Pi enters, so the sign of pi (GRChombo's Pi is
+ * "(minus) conjugate momentum") is the caller's convention;
+ * mgic_field_grchombo_vars_matter copies pi as given into component 26 ("Pi")
+ * and changes no other component.  Each entry point takes what its _punct
+ * form takes, with the table nullable too: NULL with n = 0 means the two
+ * holes of bh.  With pot all zero and pi NULL or zero they give the bits of
+ * the entry points above.  MGIC_EBADARG, before anything is launched, for
+ * what the _punct forms refuse, a non-finite pot entry and a pi of another
+ * layout.  The momentum constraint's source Pi d_i phi is not solved for: as
+ * with every A_ij input, that is the caller's responsibility. */
+MGIC_API int mgic_field_nl_coefs_matter(mgic_field psi, mgic_field phi, mgic_field acoef,
+                                        mgic_field rhs, const double bh[13], int n,
+                                        const double *table, mgic_field pi, const double pot[3]);
+MGIC_API int mgic_field_nl_integrand_matter(mgic_field psi, mgic_field phi, mgic_field out,
+                                            const double bh[13], int n, const double *table,
+                                            mgic_field pi, const double pot[3]);
+MGIC_API int mgic_field_regrid_condition_matter(mgic_field psi, mgic_field phi, mgic_field out,
+                                                const double bh[13], int n, const double *table,
+                                                mgic_field pi, const double pot[3]);
+MGIC_API int mgic_field_grchombo_vars_matter(mgic_field psi, mgic_field phi, int n, int k0, int nk,
+                                             const double bh[13], int npunct, const double *table,
+                                             mgic_field pi, const double pot[3], double *out,
+                                             int out_on_device);
 /* the field's layout: domain, periodicity, dx, number of boxes (all ranks),
  * this rank and the job size; box i's extent, owner rank and local index
  * (-1 if not local); a barrier over the field's communicator */

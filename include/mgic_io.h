@@ -83,6 +83,22 @@ MGIC_IO_API int mgic_io_write_solver_data_punct(const char *filename, int nlevel
                                                 const double *table, const int *ref_ratio,
                                                 int iter);
 
+/* The final-data writer with the stored Pi_0 (mgic.h, "Matter"): pi[l] is
+ * level l's Pi_0 field on psi[l]'s layout, copied as given into the "Pi"
+ * component (26); pi NULL: Pi = 0.  pot[3] = V0, mass, lambda is checked and
+ * otherwise unused (no written component depends on it).  Everything else as
+ * mgic_io_write_final_data_punct, with the table nullable too (NULL with
+ * npunct = 0: the two holes of bh).  A non-finite pot entry and a pi[l] of
+ * another layout are MGIC_EBADARG before the file is created.  The solver
+ * data (the reference's multigrid_vars) has no Pi component and no _matter
+ * form. */
+MGIC_IO_API int mgic_io_write_final_data_matter(const char *filename, int nlevels,
+                                                const mgic_field *psi, const mgic_field *phi,
+                                                const double bh[13], int npunct,
+                                                const double *table, const mgic_field *pi,
+                                                const double pot[3], int max_level,
+                                                const int *ref_ratio);
+
 /* The same two layouts from host arrays (tests, and callers whose data is
  * already on the host).  kind 0: final data (31 components), 1: solver data
  * (10).  Level l has nbox[l] boxes (6 ints each, all levels concatenated in

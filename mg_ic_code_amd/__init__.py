@@ -31,6 +31,7 @@ from .core import (  # noqa: F401
 )
 from .grids import set_grids  # noqa: F401
 from ._lib import IO_LIB_PATH, LIB_PATH, lib  # noqa: F401
+from .matter import Matter, PiProfile, ScalarPotential  # noqa: F401
 from .output import output_final_data, output_solver_data  # noqa: F401
 from .phi import PhiProfile  # noqa: F401
 from .punctures import Puncture, PunctureSet  # noqa: F401

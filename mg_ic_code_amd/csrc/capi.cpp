@@ -619,8 +619,25 @@ static kern::BhParams bh_params(const double bh[13]) {
 // which refuse a null one first), or null: evaluated in place.
 // table: the puncture table (the *_punct entry points, which check it first),
 // or null: the two holes of bh.
+// matter: the potential and the Pi_0 handle (the *_matter entry points, which
+// check the coefficients first), or null: rho = 0.
+struct MatterCapi {
+  kern::MatterTerms terms;  // pi unset: box_matter points it at a box
+  mgic_field pi;            // nullable: Pi = 0
+};
+static void check_matter_layout(const Grid &g, const MatterCapi *m) {
+  if (m && m->pi) check_same_layout(g, *m->pi->f, "pi");
+}
+// box n's terms (null for a null m)
+static const kern::MatterTerms *box_matter(const MatterCapi *m, int n, kern::MatterTerms &box) {
+  if (!m) return nullptr;
+  box = m->terms;
+  box.pi = m->pi ? m->pi->f->p[n] : nullptr;
+  return &box;
+}
 static void nl_coefs_capi(mgic_field psi, mgic_field phi, mgic_field acoef, mgic_field rhs,
-                          const double bh[13], const kern::PunctureTable *table = nullptr) {
+                          const double bh[13], const kern::PunctureTable *table = nullptr,
+                          const MatterCapi *matter = nullptr) {
   NEED(acoef);
   NEED(rhs);
   NEED(bh);
@@ -628,26 +645,32 @@ static void nl_coefs_capi(mgic_field psi, mgic_field phi, mgic_field acoef, mgic
   if (psi) check_same_layout(g, *psi->f, "psi");
   if (phi) check_same_layout(g, *phi->f, "phi");
   check_same_layout(g, *rhs->f, "rhs");
+  check_matter_layout(g, matter);
   const kern::BhParams p = bh_params(bh);
+  kern::MatterTerms mt;
   for (int n = 0; n < g.nlocal(); ++n)
     kern::binary_bh_coefs(acoef->f->p[n], rhs->f->p[n], psi ? psi->f->p[n] : nullptr,
                           phi ? phi->f->p[n] : nullptr, g.box_args_plain(n), g.dx, p,
-                          g.comm->stream(), table);
+                          g.comm->stream(), table, box_matter(matter, n, mt));
 }
 // gen: kern::constant_k_integrand or kern::regrid_condition
 using PsiGenerator = void (*)(double *, const double *, const double *, const BoxArgs &, double,
-                              const kern::BhParams &, hipStream_t, const kern::PunctureTable *);
+                              const kern::BhParams &, hipStream_t, const kern::PunctureTable *,
+                              const kern::MatterTerms *);
 static void psi_generator_capi(PsiGenerator gen, mgic_field psi, mgic_field phi, mgic_field out,
-                               const double bh[13], const kern::PunctureTable *table = nullptr) {
+                               const double bh[13], const kern::PunctureTable *table = nullptr,
+                               const MatterCapi *matter = nullptr) {
   NEED(out);
   NEED(bh);
   const Grid &g = *out->f->grid;
   if (psi) check_same_layout(g, *psi->f, "psi");
   if (phi) check_same_layout(g, *phi->f, "phi");
+  check_matter_layout(g, matter);
   const kern::BhParams p = bh_params(bh);
+  kern::MatterTerms mt;
   for (int n = 0; n < g.nlocal(); ++n)
     gen(out->f->p[n], psi ? psi->f->p[n] : nullptr, phi ? phi->f->p[n] : nullptr,
-        g.box_args_plain(n), g.dx, p, g.comm->stream(), table);
+        g.box_args_plain(n), g.dx, p, g.comm->stream(), table, box_matter(matter, n, mt));
 }
 MGIC_API int mgic_field_nl_coefs(mgic_field psi, mgic_field acoef, mgic_field rhs,
                                  const double bh[13]) {
@@ -681,7 +704,8 @@ static void *scratch_device(size_t bytes) {
 // phi: the stored phi_0 (the *_phi entry points), or null: evaluated in place
 static void output_vars_capi(int kind, mgic_field psi, mgic_field dpsi, mgic_field rhs, int n,
                              int k0, int nk, const double bh[13], double *out, int on_device,
-                             mgic_field phi = nullptr, const kern::PunctureTable *table = nullptr) {
+                             mgic_field phi = nullptr, const kern::PunctureTable *table = nullptr,
+                             const MatterCapi *matter = nullptr) {
   NEED(psi);
   NEED(bh);
   NEED(out);
@@ -694,6 +718,7 @@ static void output_vars_capi(int kind, mgic_field psi, mgic_field dpsi, mgic_fie
     check_same_layout(g, *rhs->f, "rhs");
   }
   if (phi) check_same_layout(g, *phi->f, "phi");
+  check_matter_layout(g, matter);
   MGIC_CHECK(n >= 0 && n < g.nlocal(), "bad local box index");
   const FabGeom &fg = g.geom[n];
   MGIC_CHECK(k0 >= 0 && nk >= 1 && k0 + nk <= fg.nz, "plane range outside the box");
@@ -705,8 +730,9 @@ static void output_vars_capi(int kind, mgic_field psi, mgic_field dpsi, mgic_fie
   double *d = out;
   if (!on_device) d = static_cast<double *>(scratch_device(bytes));
   const double *dp = kind ? dpsi->f->p[n] : nullptr, *rp = kind ? rhs->f->p[n] : nullptr;
+  kern::MatterTerms mt;
   kern::output_vars(kind, d, u.p[n], dp, rp, phi ? phi->f->p[n] : nullptr, a, k0, nk, g.dx, p, st,
-                    table);
+                    table, box_matter(matter, n, mt));
   if (!on_device) {
     MGIC_HIP(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, st));
     MGIC_HIP(hipStreamSynchronize(st));
@@ -823,6 +849,67 @@ MGIC_API int mgic_field_solver_vars_punct(mgic_field dpsi, mgic_field rhs, mgic_
   return guard([&] {
     const kern::PunctureTable t = punctures(npunct, table);
     output_vars_capi(1, psi, dpsi, rhs, n, k0, nk, bh, out, out_on_device, phi, &t);
+  });
+}
+// ---- the scalar field's kinetic and potential energy (mgic.h, "Matter"):
+// the most general form of each generator.  The table is nullable here (null
+// with n = 0: the two holes of bh); pot = V0, mass, lambda; pi: the stored
+// Pi_0 or null.  The table and pot are checked before anything else, pi's
+// layout before the first launch.
+struct MatterCall {
+  kern::PunctureTable t;
+  const kern::PunctureTable *table;
+  MatterCapi m;
+};
+static void matter_call(MatterCall &c, int n, const double *table, mgic_field pi,
+                        const double pot[3]) {
+  MGIC_CHECK(table || n == 0, "null argument: punctures (with a count that is not 0)");
+  c.table = nullptr;
+  if (table) {
+    kern::set_punctures(c.t, n, table);
+    c.table = &c.t;
+  }
+  NEED(pot);
+  c.m.terms = kern::MatterTerms{pot[0], pot[1], pot[2], nullptr};
+  kern::check_matter(c.m.terms);
+  c.m.pi = pi;
+}
+MGIC_API int mgic_field_nl_coefs_matter(mgic_field psi, mgic_field phi, mgic_field acoef,
+                                        mgic_field rhs, const double bh[13], int n,
+                                        const double *table, mgic_field pi, const double pot[3]) {
+  return guard([&] {
+    MatterCall c;
+    matter_call(c, n, table, pi, pot);
+    nl_coefs_capi(psi, phi, acoef, rhs, bh, c.table, &c.m);
+  });
+}
+MGIC_API int mgic_field_nl_integrand_matter(mgic_field psi, mgic_field phi, mgic_field out,
+                                            const double bh[13], int n, const double *table,
+                                            mgic_field pi, const double pot[3]) {
+  return guard([&] {
+    MatterCall c;
+    matter_call(c, n, table, pi, pot);
+    psi_generator_capi(kern::constant_k_integrand, psi, phi, out, bh, c.table, &c.m);
+  });
+}
+MGIC_API int mgic_field_regrid_condition_matter(mgic_field psi, mgic_field phi, mgic_field out,
+                                                const double bh[13], int n, const double *table,
+                                                mgic_field pi, const double pot[3]) {
+  return guard([&] {
+    MatterCall c;
+    matter_call(c, n, table, pi, pot);
+    psi_generator_capi(kern::regrid_condition, psi, phi, out, bh, c.table, &c.m);
+  });
+}
+MGIC_API int mgic_field_grchombo_vars_matter(mgic_field psi, mgic_field phi, int n, int k0, int nk,
+                                             const double bh[13], int npunct, const double *table,
+                                             mgic_field pi, const double pot[3], double *out,
+                                             int out_on_device) {
+  return guard([&] {
+    MatterCall c;
+    matter_call(c, npunct, table, pi, pot);
+    output_vars_capi(0, psi, nullptr, nullptr, n, k0, nk, bh, out, out_on_device, phi, c.table,
+                     &c.m);
   });
 }
 MGIC_API int mgic_field_norm(mgic_field x, int ord, double *out) {

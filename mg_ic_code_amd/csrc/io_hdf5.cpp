@@ -378,9 +378,12 @@ namespace {
 // phi: null (phi_0 evaluated in place), or one stored phi_0 field per level
 // table: null (the two holes of bh), or npunct punctures of 10 doubles each;
 // the library checks it at the first box, before it launches anything
+// pot: null (today's components), or V0, mass, lambda with pi null (Pi = 0)
+// or one stored Pi_0 field per level, which becomes the component "Pi"
 int write_final_data(const char *filename, int nlevels, const mgic_field *psi,
                      const mgic_field *phi, const double bh[13], int max_level,
-                     const int *ref_ratio, int npunct = 0, const double *table = nullptr) {
+                     const int *ref_ratio, int npunct = 0, const double *table = nullptr,
+                     const mgic_field *pi = nullptr, const double *pot = nullptr) {
   return guard([&] {
     need(psi, "psi");
     need(bh, "bh");
@@ -396,7 +399,11 @@ int write_final_data(const char *filename, int nlevels, const mgic_field *psi,
     for (int l = 0; phi && l < nlevels; ++l) need(phi[l], "phi[l]");
     write_fields(filename ? filename : "vcPoissonFinal.3d.hdf5", J, lead,
                  [&](int l, int n, int k0, int nk, double *out) {
-                   if (table)
+                   if (pot)
+                     mg(mgic_field_grchombo_vars_matter(psi[l], phi ? phi[l] : nullptr, n, k0, nk,
+                                                        bh, npunct, table, pi ? pi[l] : nullptr,
+                                                        pot, out, 0));
+                   else if (table)
                      mg(mgic_field_grchombo_vars_punct(psi[l], phi ? phi[l] : nullptr, n, k0, nk,
                                                        bh, npunct, table, out, 0));
                    else if (phi)
@@ -499,6 +506,49 @@ MGIC_IO_API int mgic_io_write_final_data_punct(const char *filename, int nlevels
   const int st = guard([&] { check_punctures(npunct, table); });
   if (st != MGIC_OK) return st;
   return write_final_data(filename, nlevels, psi, phi, bh, max_level, ref_ratio, npunct, table);
+}
+
+// pi[l] must have psi[l]'s layout (the library checks again per box): the
+// same domain, cell size and boxes with the same owners
+static void check_pi_layout(mgic_field psi, mgic_field pi) {
+  int dom[2][6], per[3], nbox[2] = {0, 0}, rank = 0, size = 1;
+  double dx[2];
+  const mgic_field f[2] = {psi, pi};
+  for (int s = 0; s < 2; ++s) mg(mgic_field_layout(f[s], dom[s], per, &dx[s], &nbox[s], &rank, &size));
+  bool ok = nbox[0] == nbox[1] && dx[0] == dx[1];
+  for (int d = 0; ok && d < 6; ++d) ok = dom[0][d] == dom[1][d];
+  for (int b = 0; ok && b < nbox[0]; ++b) {
+    int lohi[2][6], owner[2];
+    for (int s = 0; s < 2; ++s) mg(mgic_field_box(f[s], b, lohi[s], &owner[s], nullptr));
+    ok = owner[0] == owner[1];
+    for (int d = 0; ok && d < 6; ++d) ok = lohi[0][d] == lohi[1][d];
+  }
+  if (!ok) throw IoError(MGIC_EBADARG, "layout mismatch: pi");
+}
+
+MGIC_IO_API int mgic_io_write_final_data_matter(const char *filename, int nlevels,
+                                                const mgic_field *psi, const mgic_field *phi,
+                                                const double bh[13], int npunct,
+                                                const double *table, const mgic_field *pi,
+                                                const double pot[3], int max_level,
+                                                const int *ref_ratio) {
+  const int st = guard([&] {
+    if (table || npunct != 0) check_punctures(npunct, table);
+    need(pot, "pot");
+    for (int c = 0; c < 3; ++c)
+      if (!std::isfinite(pot[c]))
+        throw IoError(MGIC_EBADARG, "potential coefficients (V0, mass, lambda) must be finite");
+    need(psi, "psi");
+    if (nlevels < 1) throw IoError(MGIC_EBADARG, "nlevels < 1");
+    for (int l = 0; pi && l < nlevels; ++l) {
+      need(psi[l], "psi[l]");
+      need(pi[l], "pi[l]");
+      check_pi_layout(psi[l], pi[l]);
+    }
+  });
+  if (st != MGIC_OK) return st;
+  return write_final_data(filename, nlevels, psi, phi, bh, max_level, ref_ratio, npunct, table, pi,
+                          pot);
 }
 
 MGIC_IO_API int mgic_io_write_solver_data_punct(const char *filename, int nlevels,

@@ -1041,19 +1041,50 @@ __device__ __forceinline__ double bh_rho_grad(const BhParams &p, const double *_
   }
 }
 
+// the energy density set_m_value takes (SetLevelData.cpp:266-278), chosen at
+// compile time.  MATTER: rho = 0.5 * Pi * Pi + V(phi0) with the coefficients
+// and the stored Pi_0 of `m` (kernels.hpp MatterTerms; a null pi, the same
+// for every lane, is Pi = 0); else the reference's literal zeros, `m` empty
+// and phi0 unused.
+template <bool MATTER> struct MatterArg { };
+template <> struct MatterArg<true> { MatterTerms m; };
+template <bool MATTER>
+__device__ __forceinline__ double bh_rho(const MatterArg<MATTER> &m, double phi0, long idx) {
+  if constexpr (MATTER) {
+    const double Pi_field = m.m.pi ? m.m.pi[idx] : 0.0;
+    const double V_of_phi = m.m.V0 + 0.5 * m.m.mass * m.m.mass * phi0 * phi0 +
+                            0.25 * m.m.lambda * phi0 * phi0 * phi0 * phi0;
+    return 0.5 * Pi_field * Pi_field + V_of_phi;
+  } else {
+    return 0.5 * 0.0 * 0.0 + 0.0;
+  }
+}
+// phi_0 at the cell for bh_rho: evaluated (or loaded) with MATTER alone
+template <bool MATTER, bool STORED>
+__device__ __forceinline__ double bh_rho_phi0(const BhParams &p, const double *__restrict__ phi,
+                                              const int iv[3], long idx, double dx) {
+  if constexpr (MATTER) {
+    return bh_phi0<STORED>(p, phi, iv, idx, dx);
+  } else {
+    return 0.0;
+  }
+}
+
 // set_a_coef + set_rhs (SetLevelData.cpp:73-127, :281-325); psi == nullptr:
 // psi = 1 everywhere (NL iteration 0), else psi read with its ghost layer
 // INTEGRAND: set_constant_K_integrand (SetLevelData.cpp:131-180) into acoef
 // instead (m taken at K = 0, rhs untouched)
 // STORED: phi_0 read from `phi` with its ghost layer (see bh_phi0)
 // TABLE: the holes of the puncture table `t` (see bh_terms)
-template <bool INTEGRAND, bool STORED, bool TABLE>
+// MATTER: rho from the potential and the stored Pi_0 of `mt` (see bh_rho)
+template <bool INTEGRAND, bool STORED, bool TABLE, bool MATTER>
 __global__ __launch_bounds__(256) void k_binary_bh(double *__restrict__ acoef,
                                                    double *__restrict__ rhs,
                                                    const double *__restrict__ psi,
                                                    const double *__restrict__ phi,
                                                    const BoxArgs g, double dx, const BhParams p,
-                                                   const PunctureArg<TABLE> t) {
+                                                   const PunctureArg<TABLE> t,
+                                                   const MatterArg<MATTER> mt) {
   const int i = blockIdx.x * TX + threadIdx.x;
   const int j = blockIdx.y * TY + threadIdx.y;
   const int k = blockIdx.z;
@@ -1063,7 +1094,7 @@ __global__ __launch_bounds__(256) void k_binary_bh(double *__restrict__ acoef,
   const double rho_grad = bh_rho_grad<STORED>(p, phi, iv, idx, g, dx);
   const BhBowenYork c = bh_terms<TABLE>(p, t, iv, dx);
   const double A2 = bh_A2(c);
-  const double rho = 0.5 * 0.0 * 0.0 + 0.0;
+  const double rho = bh_rho<MATTER>(mt, bh_rho_phi0<MATTER, STORED>(p, phi, iv, idx, dx), idx);
   const double K = INTEGRAND ? 0.0 : p.constant_K;  // set_m_value(.., 0.0) for the integrand
   const double m = (2.0 / 3.0) * (K * K) - 16.0 * M_PI * p.G_Newton * rho;
   const double psi_c = psi ? psi[idx] : 1.0;
@@ -1092,13 +1123,15 @@ __global__ __launch_bounds__(256) void k_binary_bh(double *__restrict__ acoef,
 // right after set_initial_conditions).  No ghost cell of psi is read.
 // STORED: phi_0 read from `phi` with its ghost layer (see bh_phi0)
 // TABLE: the holes of the puncture table `t` (see bh_terms)
-template <bool STORED, bool TABLE>
+// MATTER: rho from the potential and the stored Pi_0 of `mt` (see bh_rho)
+template <bool STORED, bool TABLE, bool MATTER>
 __global__ __launch_bounds__(256) void k_regrid_condition(double *__restrict__ out,
                                                           const double *__restrict__ psi,
                                                           const double *__restrict__ phi,
                                                           const BoxArgs g, double dx,
                                                           const BhParams p,
-                                                          const PunctureArg<TABLE> t) {
+                                                          const PunctureArg<TABLE> t,
+                                                          const MatterArg<MATTER> mt) {
   const int i = blockIdx.x * TX + threadIdx.x;
   const int j = blockIdx.y * TY + threadIdx.y;
   const int k = blockIdx.z;
@@ -1108,7 +1141,7 @@ __global__ __launch_bounds__(256) void k_regrid_condition(double *__restrict__ o
   const double rho_grad = bh_rho_grad<STORED>(p, phi, iv, idx, g, dx);
   const BhBowenYork c = bh_terms<TABLE>(p, t, iv, dx);
   const double A2 = bh_A2(c);
-  const double rho = 0.5 * 0.0 * 0.0 + 0.0;
+  const double rho = bh_rho<MATTER>(mt, bh_rho_phi0<MATTER, STORED>(p, phi, iv, idx, dx), idx);
   const double m = (2.0 / 3.0) * (0.0 * 0.0) - 16.0 * M_PI * p.G_Newton * rho;  // K = 0 (:219)
   const double psi_0 = (psi ? psi[idx] : 1.0) + c.psi_bh;  // :232-233
   out[idx] = 1.5 * fabs(m) + 1.5 * A2 * pow(psi_0, -7.0) +
@@ -1204,7 +1237,9 @@ __global__ __launch_bounds__(256) void k_rho_grad_phi(double *__restrict__ r,
 //         phi_0 of set_initial_conditions, SetLevelData.cpp:31-72)
 // STORED: phi (KIND 0, v[25]) / phi_0 (KIND 1) copied from `phi` (see bh_phi0)
 // TABLE: the holes of the puncture table `t` (see bh_terms)
-template <int KIND, bool STORED, bool TABLE>
+// MATTER (KIND 0): Pi (v[26]) copied from the stored Pi_0 of `mt`, as given
+// (a null pi: 0); the potential is not read
+template <int KIND, bool STORED, bool TABLE, bool MATTER>
 __global__ __launch_bounds__(256) void k_output_vars(double *__restrict__ out,
                                                      const double *__restrict__ psi,
                                                      const double *__restrict__ dpsi,
@@ -1212,7 +1247,8 @@ __global__ __launch_bounds__(256) void k_output_vars(double *__restrict__ out,
                                                      const double *__restrict__ phi,
                                                      const BoxArgs g, int k0, int nk, double dx,
                                                      const BhParams p,
-                                                     const PunctureArg<TABLE> t) {
+                                                     const PunctureArg<TABLE> t,
+                                                     const MatterArg<MATTER> mt) {
   const int i = blockIdx.x * TX + threadIdx.x;
   const int j = blockIdx.y * TY + threadIdx.y;
   const int k = blockIdx.z;
@@ -1241,6 +1277,7 @@ __global__ __launch_bounds__(256) void k_output_vars(double *__restrict__ out,
   v[7] = p.constant_K;                               // K (:371)
   v[0] = chi;
   v[25] = phi0;                                      // phi (:387)
+  if constexpr (MATTER) v[26] = mt.m.pi ? mt.m.pi[idx] : 0.0;  // Pi: the stored Pi_0
   v[8] = b.A11 * factor;                             // A11 .. A33 (:388-393)
   v[9] = b.A12 * factor;
   v[10] = b.A13 * factor;
@@ -2152,59 +2189,94 @@ static PunctureArg<true> table_arg(const PunctureTable *t) {
   a.t = *t;
   return a;
 }
+// matter null (rho the literal zero) or given: one more instantiation choice
+void check_matter(const MatterTerms &m) {
+  if (!std::isfinite(m.V0) || !std::isfinite(m.mass) || !std::isfinite(m.lambda))
+    throw Error(kBadArg, "potential coefficients (V0, mass, lambda) must be finite");
+}
+static MatterArg<true> matter_arg(const MatterTerms *m) {
+  MatterArg<true> a;
+  a.m = *m;
+  return a;
+}
 
-template <bool INTEGRAND>
+template <bool INTEGRAND, bool MATTER>
 static void launch_binary_bh(double *acoef, double *rhs, const double *psi, const double *phi,
                              const BoxArgs &g, double dx, const BhParams &p,
-                             const PunctureTable *t, hipStream_t st) {
-  check_table(t);
-  if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
+                             const PunctureTable *t, const MatterArg<MATTER> &m, hipStream_t st) {
   const dim3 grid = grid_cells(g.nx, g.ny, g.nz);
   const PunctureArg<false> none;
   if (t && phi)
-    k_binary_bh<INTEGRAND, true, true><<<grid, kBlock, 0, st>>>(acoef, rhs, psi, phi, g, dx, p,
-                                                                table_arg(t));
+    k_binary_bh<INTEGRAND, true, true, MATTER><<<grid, kBlock, 0, st>>>(acoef, rhs, psi, phi, g,
+                                                                        dx, p, table_arg(t), m);
   else if (t)
-    k_binary_bh<INTEGRAND, false, true><<<grid, kBlock, 0, st>>>(acoef, rhs, psi, nullptr, g, dx,
-                                                                 p, table_arg(t));
+    k_binary_bh<INTEGRAND, false, true, MATTER><<<grid, kBlock, 0, st>>>(
+        acoef, rhs, psi, nullptr, g, dx, p, table_arg(t), m);
   else if (phi)
-    k_binary_bh<INTEGRAND, true, false><<<grid, kBlock, 0, st>>>(acoef, rhs, psi, phi, g, dx, p,
-                                                                 none);
+    k_binary_bh<INTEGRAND, true, false, MATTER><<<grid, kBlock, 0, st>>>(acoef, rhs, psi, phi, g,
+                                                                         dx, p, none, m);
   else
-    k_binary_bh<INTEGRAND, false, false><<<grid, kBlock, 0, st>>>(acoef, rhs, psi, nullptr, g, dx,
-                                                                  p, none);
+    k_binary_bh<INTEGRAND, false, false, MATTER><<<grid, kBlock, 0, st>>>(acoef, rhs, psi, nullptr,
+                                                                          g, dx, p, none, m);
   check_launch();
+}
+template <bool INTEGRAND>
+static void launch_binary_bh(double *acoef, double *rhs, const double *psi, const double *phi,
+                             const BoxArgs &g, double dx, const BhParams &p,
+                             const PunctureTable *t, const MatterTerms *m, hipStream_t st) {
+  check_table(t);
+  if (m) check_matter(*m);
+  if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
+  if (m)
+    launch_binary_bh<INTEGRAND, true>(acoef, rhs, psi, phi, g, dx, p, t, matter_arg(m), st);
+  else
+    launch_binary_bh<INTEGRAND, false>(acoef, rhs, psi, phi, g, dx, p, t, MatterArg<false>(), st);
 }
 
 void binary_bh_coefs(double *acoef, double *rhs, const double *psi, const double *phi,
                      const BoxArgs &g, double dx, const BhParams &p, hipStream_t st,
-                     const PunctureTable *table) {
-  launch_binary_bh<false>(acoef, rhs, psi, phi, g, dx, p, table, st);
+                     const PunctureTable *table, const MatterTerms *matter) {
+  launch_binary_bh<false>(acoef, rhs, psi, phi, g, dx, p, table, matter, st);
 }
 
 void constant_k_integrand(double *out, const double *psi, const double *phi, const BoxArgs &g,
                           double dx, const BhParams &p, hipStream_t st,
-                          const PunctureTable *table) {
-  launch_binary_bh<true>(out, nullptr, psi, phi, g, dx, p, table, st);
+                          const PunctureTable *table, const MatterTerms *matter) {
+  launch_binary_bh<true>(out, nullptr, psi, phi, g, dx, p, table, matter, st);
 }
 
-void regrid_condition(double *out, const double *psi, const double *phi, const BoxArgs &g,
-                      double dx, const BhParams &p, hipStream_t st, const PunctureTable *table) {
-  check_table(table);
-  if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
+template <bool MATTER>
+static void launch_regrid_condition(double *out, const double *psi, const double *phi,
+                                    const BoxArgs &g, double dx, const BhParams &p,
+                                    const PunctureTable *table, const MatterArg<MATTER> &m,
+                                    hipStream_t st) {
   const dim3 grid = grid_cells(g.nx, g.ny, g.nz);
   const PunctureArg<false> none;
   if (table && phi)
-    k_regrid_condition<true, true><<<grid, kBlock, 0, st>>>(out, psi, phi, g, dx, p,
-                                                            table_arg(table));
+    k_regrid_condition<true, true, MATTER><<<grid, kBlock, 0, st>>>(out, psi, phi, g, dx, p,
+                                                                    table_arg(table), m);
   else if (table)
-    k_regrid_condition<false, true><<<grid, kBlock, 0, st>>>(out, psi, nullptr, g, dx, p,
-                                                             table_arg(table));
+    k_regrid_condition<false, true, MATTER><<<grid, kBlock, 0, st>>>(out, psi, nullptr, g, dx, p,
+                                                                     table_arg(table), m);
   else if (phi)
-    k_regrid_condition<true, false><<<grid, kBlock, 0, st>>>(out, psi, phi, g, dx, p, none);
+    k_regrid_condition<true, false, MATTER><<<grid, kBlock, 0, st>>>(out, psi, phi, g, dx, p, none,
+                                                                     m);
   else
-    k_regrid_condition<false, false><<<grid, kBlock, 0, st>>>(out, psi, nullptr, g, dx, p, none);
+    k_regrid_condition<false, false, MATTER><<<grid, kBlock, 0, st>>>(out, psi, nullptr, g, dx, p,
+                                                                      none, m);
   check_launch();
+}
+
+void regrid_condition(double *out, const double *psi, const double *phi, const BoxArgs &g,
+                      double dx, const BhParams &p, hipStream_t st, const PunctureTable *table,
+                      const MatterTerms *matter) {
+  check_table(table);
+  if (matter) check_matter(*matter);
+  if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
+  if (matter)
+    launch_regrid_condition<true>(out, psi, phi, g, dx, p, table, matter_arg(matter), st);
+  else
+    launch_regrid_condition<false>(out, psi, phi, g, dx, p, table, MatterArg<false>(), st);
 }
 
 void tag_lattice(unsigned char *mask, const double *cond, const BoxArgs &g, double tag_val,
@@ -2236,36 +2308,41 @@ void rho_grad_phi(double *r, const double *phi, const BoxArgs &g, double dx, hip
   check_launch();
 }
 
-template <int KIND>
+template <int KIND, bool MATTER>
 static void launch_output_vars(double *out, const double *psi, const double *dpsi,
                                const double *rhs, const double *phi, const BoxArgs &g, int k0,
                                int nk, double dx, const BhParams &p, const PunctureTable *t,
-                               hipStream_t st) {
+                               const MatterArg<MATTER> &m, hipStream_t st) {
   const dim3 grid = grid_cells(g.nx, g.ny, nk);
   const PunctureArg<false> none;
   if (t && phi)
-    k_output_vars<KIND, true, true><<<grid, kBlock, 0, st>>>(out, psi, dpsi, rhs, phi, g, k0, nk,
-                                                             dx, p, table_arg(t));
+    k_output_vars<KIND, true, true, MATTER><<<grid, kBlock, 0, st>>>(
+        out, psi, dpsi, rhs, phi, g, k0, nk, dx, p, table_arg(t), m);
   else if (t)
-    k_output_vars<KIND, false, true><<<grid, kBlock, 0, st>>>(out, psi, dpsi, rhs, nullptr, g, k0,
-                                                              nk, dx, p, table_arg(t));
+    k_output_vars<KIND, false, true, MATTER><<<grid, kBlock, 0, st>>>(
+        out, psi, dpsi, rhs, nullptr, g, k0, nk, dx, p, table_arg(t), m);
   else if (phi)
-    k_output_vars<KIND, true, false><<<grid, kBlock, 0, st>>>(out, psi, dpsi, rhs, phi, g, k0, nk,
-                                                              dx, p, none);
+    k_output_vars<KIND, true, false, MATTER><<<grid, kBlock, 0, st>>>(out, psi, dpsi, rhs, phi, g,
+                                                                      k0, nk, dx, p, none, m);
   else
-    k_output_vars<KIND, false, false><<<grid, kBlock, 0, st>>>(out, psi, dpsi, rhs, nullptr, g,
-                                                               k0, nk, dx, p, none);
+    k_output_vars<KIND, false, false, MATTER><<<grid, kBlock, 0, st>>>(
+        out, psi, dpsi, rhs, nullptr, g, k0, nk, dx, p, none, m);
 }
 
 void output_vars(int kind, double *out, const double *psi, const double *dpsi, const double *rhs,
                  const double *phi, const BoxArgs &g, int k0, int nk, double dx, const BhParams &p,
-                 hipStream_t st, const PunctureTable *table) {
+                 hipStream_t st, const PunctureTable *table, const MatterTerms *matter) {
   check_table(table);
+  if (matter) check_matter(*matter);
   if (g.nx <= 0 || g.ny <= 0 || nk <= 0) return;
-  if (kind == 0)
-    launch_output_vars<0>(out, psi, dpsi, rhs, phi, g, k0, nk, dx, p, table, st);
-  else
-    launch_output_vars<1>(out, psi, dpsi, rhs, phi, g, k0, nk, dx, p, table, st);
+  const MatterArg<false> none;
+  if (kind == 0 && matter)
+    launch_output_vars<0, true>(out, psi, dpsi, rhs, phi, g, k0, nk, dx, p, table,
+                                matter_arg(matter), st);
+  else if (kind == 0)
+    launch_output_vars<0, false>(out, psi, dpsi, rhs, phi, g, k0, nk, dx, p, table, none, st);
+  else  // the solver data has no Pi
+    launch_output_vars<1, false>(out, psi, dpsi, rhs, phi, g, k0, nk, dx, p, table, none, st);
   check_launch();
 }
 

@@ -217,7 +217,21 @@ struct PunctureTable {
 // fill t from 10 n values in row order; throws kBadArg on a count outside
 // 1 .. kMaxPunctures, a null `values` or a non-finite entry
 void set_punctures(PunctureTable &t, int n, const double *values);
+// The scalar field's kinetic and potential energy, the slot set_m_value
+// (SetLevelData.cpp:266-278) leaves at zero: rho = 0.5 * Pi * Pi + V(phi_0),
+// V(phi) = V0 + 0.5 * mass * mass * phi * phi + 0.25 * lambda * phi * phi *
+// phi * phi, evaluated left to right.  pi: the stored Pi_0 of the box, one
+// value per cell on the layout of the other fields (valid cells only are
+// read), or nullptr: Pi = 0.  Passed to the kernels by value.
+struct MatterTerms {
+  double V0, mass, lambda;
+  const double *pi;
+};
+// throws kBadArg on a non-finite coefficient
+void check_matter(const MatterTerms &m);
 // psi: nullptr = psi 1 everywhere, else read with its ghost layer
+// matter (here and below): nullptr = rho is the reference's literal zero,
+// else the terms above
 // table (here and below): nullptr = the two holes of BhParams, else the
 // puncture table (the six hole entries of BhParams are then unused)
 // phi (here and in the generators below): nullptr = phi_0 is MyPhiFunction.H's
@@ -225,15 +239,16 @@ void set_punctures(PunctureTable &t, int n, const double *values);
 // its one ghost layer next to each face
 void binary_bh_coefs(double *acoef, double *rhs, const double *psi, const double *phi,
                      const BoxArgs &g, double dx, const BhParams &p, hipStream_t st,
-                     const PunctureTable *table = nullptr);
+                     const PunctureTable *table = nullptr, const MatterTerms *matter = nullptr);
 // set_constant_K_integrand (SetLevelData.cpp:131-180) at psi (nullptr: 1)
 void constant_k_integrand(double *out, const double *psi, const double *phi, const BoxArgs &g,
                           double dx, const BhParams &p, hipStream_t st,
-                          const PunctureTable *table = nullptr);
+                          const PunctureTable *table = nullptr,
+                          const MatterTerms *matter = nullptr);
 // set_regrid_condition (SetLevelData.cpp:190-240) at psi (nullptr: 1)
 void regrid_condition(double *out, const double *psi, const double *phi, const BoxArgs &g,
                       double dx, const BhParams &p, hipStream_t st,
-                      const PunctureTable *table = nullptr);
+                      const PunctureTable *table = nullptr, const MatterTerms *matter = nullptr);
 // set_tag_cells (SetGrids.cpp:172-207) of one box onto a byte mask over lattice
 // cells [lat_lo, lat_lo + lat_n) (lattice index = floor(cell / c), x fastest):
 // cells with |cond| >= tag_val, grown by `grow` and clipped to [dom_lo,
@@ -247,11 +262,13 @@ void rho_grad_phi(double *r, const double *phi, const BoxArgs &g, double dx, hip
 // WriteOutput.H's components for planes [k0, k0+nk) of a valid box,
 // component-major, i fastest.  kind 0: the 31 GRChombo variables of
 // set_output_data (psi); kind 1: output_solver_data's dpsi, rhs, psi, A_ij_0,
-// phi_0
+// phi_0.  matter (kind 0 only; kind 1 has no Pi): its pi, as stored, is
+// component 26 ("Pi"; nullptr or a null pi: 0)
 constexpr int kNumGRChomboVars = 31, kNumSolverVars = 10;
 void output_vars(int kind, double *out, const double *psi, const double *dpsi, const double *rhs,
                  const double *phi, const BoxArgs &g, int k0, int nk, double dx, const BhParams &p,
-                 hipStream_t st, const PunctureTable *table = nullptr);
+                 hipStream_t st, const PunctureTable *table = nullptr,
+                 const MatterTerms *matter = nullptr);
 // ---- phi_0 as a stored field (SetLevelData.cpp:32-71's c_phi_0): the profile
 // at every cell centre of the box grown by one, for the generators' `phi`
 enum PhiProfile { kPhiGaussian = 0, kPhiSine = 1 };  // MyPhiFunction.H:14-15, :18-20

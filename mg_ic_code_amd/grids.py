@@ -30,6 +30,8 @@ import numpy as np
 
 from ._lib import call
 from .core import BH_KEYS, Box6, Grid, LevelData, _ints, gloo_allgather
+from .matter import (FilledMatter, MatterArgumentError, PiProfile, resolve_matter,
+                     set_regrid_condition_matter)
 from .params import PoissonParameters
 from .phi import PhiArgumentError, PhiProfile, set_regrid_condition_phi
 from .punctures import resolve_punctures, set_regrid_condition_punct
@@ -131,7 +133,8 @@ def _level_max_norm(cond: LevelData) -> float:
 
 
 def set_grids(comm, prm: PoissonParameters, base_grid: Grid, max_level: Optional[int] = None,
-              allgather=None, phi0: Optional[PhiProfile] = None, punctures=None) -> List[Grid]:
+              allgather=None, phi0: Optional[PhiProfile] = None, punctures=None,
+              matter=None) -> List[Grid]:
     """The hierarchy set_grids generates over `base_grid` (level 0, covering
     the domain): [base_grid, Grid(patches=True) of level 1, ...], at most
     max_level (default prm.max_level) levels above the base.  comm.size > 1:
@@ -142,11 +145,20 @@ def set_grids(comm, prm: PoissonParameters, base_grid: Grid, max_level: Optional
     taken) and read by the stored-field regrid condition.
     punctures: None -- the deck's table (prm.punctures) if it has one, else the
     deck's two holes; else a punctures.PunctureSet, read by the table form of
-    the regrid condition."""
+    the regrid condition.
+    matter: None -- the deck's (prm.matter) if it has one, else no matter; else
+    a matter.Matter whose pi is None or a PiProfile (levels appear and must be
+    filled, so pre-filled fields cannot be taken): rho enters the regrid
+    condition through 1.5 |m|."""
     if phi0 is not None and not isinstance(phi0, PhiProfile):
         raise PhiArgumentError("set_grids", "phi0 must be a PhiProfile (levels appear and must "
                                f"be filled), not {type(phi0).__name__}")
     punct = resolve_punctures(punctures, prm)
+    mat = resolve_matter(matter, prm, "set_grids")
+    if mat is not None and (isinstance(mat, FilledMatter) or
+                            not (mat.pi is None or isinstance(mat.pi, PiProfile))):
+        raise MatterArgumentError("set_grids", "matter.pi must be None or a PiProfile (levels "
+                                  "appear and must be filled), not pre-filled fields")
     max_level = prm.max_level if max_level is None else int(max_level)
     c, _ = regrid_lattice(prm.block_factor, prm.max_grid_size)
     if comm.size > 1 and allgather is None:
@@ -161,7 +173,12 @@ def set_grids(comm, prm: PoissonParameters, base_grid: Grid, max_level: Optional
         tags = []
         for g in grids:
             cond = LevelData(g)
-            if punct is not None:
+            if mat is not None:
+                set_regrid_condition_matter(
+                    None, cond, bh, mat.potential,
+                    mat.pi.fill(g, bh) if mat.pi is not None else None, punct,
+                    phi0.fill(g, bh) if phi0 is not None else None)
+            elif punct is not None:
                 set_regrid_condition_punct(None, cond, bh, punct,
                                            phi=phi0.fill(g, bh) if phi0 is not None else None)
             elif phi0 is None:

@@ -46,6 +46,7 @@ from .core import (AMRMultiGrid, AMRSolver, BiCGStabSolver, Grid, LevelData, Mul
                    OperatorParams, SolverParams, defineOperatorFactory, set_nl_coefs, BH_KEYS)
 from ._lib import call
 from .output import output_final_data, output_solver_data
+from .matter import fill_matter, set_nl_coefs_matter, set_nl_integrand_matter
 from .params import PoissonParameters
 from .phi import resolve_phi0, set_nl_coefs_phi, set_nl_integrand_phi
 from .punctures import resolve_punctures, set_nl_coefs_punct, set_nl_integrand_punct
@@ -81,10 +82,13 @@ def set_nl_integrand(psi: LevelData, out: LevelData, bh: dict) -> None:
     call("mgic_field_nl_integrand", psi.handle, out.handle, vals)
 
 
-def _coefs(psi, phi, a, rhs, bh, punct=None) -> None:
+def _coefs(psi, phi, a, rhs, bh, punct=None, mat=None, lev=0) -> None:
     """set_a_coef + set_rhs: analytic phi_0 (phi None) or the stored field; the
-    deck's two holes (punct None) or the puncture table."""
-    if punct is not None:
+    deck's two holes (punct None) or the puncture table; no matter (mat None:
+    today's calls) or the filled matter's potential and its Pi_0 of level lev."""
+    if mat is not None:
+        set_nl_coefs_matter(psi, a, rhs, bh, mat.potential, mat.level(lev), punct, phi)
+    elif punct is not None:
         set_nl_coefs_punct(psi, a, rhs, bh, punct, phi=phi)
     elif phi is None:
         set_nl_coefs(psi, a, rhs, bh)
@@ -92,8 +96,10 @@ def _coefs(psi, phi, a, rhs, bh, punct=None) -> None:
         set_nl_coefs_phi(psi, phi, a, rhs, bh)
 
 
-def _integrand(psi, phi, out, bh, punct=None) -> None:
-    if punct is not None:
+def _integrand(psi, phi, out, bh, punct=None, mat=None, lev=0) -> None:
+    if mat is not None:
+        set_nl_integrand_matter(psi, out, bh, mat.potential, mat.level(lev), punct, phi)
+    elif punct is not None:
         set_nl_integrand_punct(psi, out, bh, punct, phi=phi)
     elif phi is None:
         set_nl_integrand(psi, out, bh)
@@ -104,7 +110,8 @@ def _integrand(psi, phi, out, bh, punct=None) -> None:
 def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
                   prolong_type: int = 1, bottom_solver: int = 1,
                   max_NL_iterations: Optional[int] = None,
-                  output_dir: Optional[str] = None, phi0=None, punctures=None) -> NLResult:
+                  output_dir: Optional[str] = None, phi0=None, punctures=None,
+                  matter=None) -> NLResult:
     """phi0: None -- the analytic Gaussian, evaluated in the kernels; else a
     phi.PhiProfile, or one pre-filled LevelData per level: phi_0 is stored once
     before the NL loop (set_initial_conditions, SetLevelData.cpp:32-71) and the
@@ -112,13 +119,18 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
     punctures: None -- the deck's table (prm.punctures) if it has one, else
     the deck's two holes through today's entry points; else a
     punctures.PunctureSet: the table generators and writers are used
-    throughout."""
+    throughout.
+    matter: None -- the deck's (prm.matter) if it has one, else no matter
+    (rho = 0, today's calls); else a matter.Matter: rho = 0.5 Pi^2 + V(phi_0)
+    enters m in the coefficients and the K integrand, Pi_0 is stored once
+    before the NL loop, and the final data carry it as "Pi"."""
     punct = resolve_punctures(punctures, prm)
     if isinstance(grid, (list, tuple)):
         if len(grid) > 1:
             return _poisson_solve_amr(list(grid), prm, max_depth, prolong_type, bottom_solver,
-                                      max_NL_iterations, output_dir, phi0, punct)
+                                      max_NL_iterations, output_dir, phi0, punct, matter)
         grid = grid[0]
+    mat = fill_matter(matter, [grid], prm)
     phis = resolve_phi0(phi0, [grid], prm)
     phi = phis[0] if phis is not None else None
     periodic = bool(prm.is_periodic)
@@ -147,12 +159,12 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
                 integrand, ones = LevelData(grid), LevelData(grid)
                 ones.set_val(1.0)
             bh["constant_K"] = 0.0
-            _integrand(psi, phi, integrand, bh, punct)
+            _integrand(psi, phi, integrand, bh, punct, mat)
             tmp_op = defineOperatorFactory(grid, a, b, op_params).AMRnewOp()
             integral = tmp_op.dotProduct(integrand, ones) * dx ** 3  # computeSum
             bh["constant_K"] = -math.sqrt(abs(integral) / volume)
             res.constant_K.append(bh["constant_K"])
-        _coefs(psi, phi, a, rhs, bh, punct)  # :155-161
+        _coefs(psi, phi, a, rhs, bh, punct, mat)  # :155-161
         fac = defineOperatorFactory(grid, a, b, op_params)
         # N > 1: depths whose boxes are below 32 cells a side are gathered to
         # one box on rank 0 (the coarsest levels solved on rank 0)
@@ -181,7 +193,7 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
         def write():
             output_final_data([psi], bh, prm.max_level, [2],
                               os.path.join(output_dir, "vcPoissonFinal.3d.hdf5"), phi=phis,
-                              punctures=punct)
+                              punctures=punct, matter=mat)
     return finish_nl_loop(res, write)
 
 
@@ -194,7 +206,8 @@ def _op_params(prm: PoissonParameters, prolong_type: int) -> OperatorParams:
 
 def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int,
                        prolong_type: int, bottom_solver: int, max_NL_iterations: Optional[int],
-                       output_dir: Optional[str], phi0=None, punct=None) -> NLResult:
+                       output_dir: Optional[str], phi0=None, punct=None,
+                       matter=None) -> NLResult:
     """poissonSolve over nlevels = len(grids) AMR levels (Main_PoissonSolver.cpp:51-250)."""
     periodic = bool(prm.is_periodic)
     if periodic != all(grids[0].periodic):
@@ -209,6 +222,7 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
         psi[l].set_val_all(1.0)
         dpsi[l].set_zero()
         b[l].set_val(1.0)
+    mat = fill_matter(matter, grids, prm)
     phis = resolve_phi0(phi0, grids, prm)
     phi = phis if phis is not None else [None] * nlev
     bh = prm.bh(constant_K=0.0)
@@ -230,12 +244,12 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
                 geom = AMRSolver(list(zip(grids, a, b)), op_params, sp)
             bh["constant_K"] = 0.0
             for l in range(nlev):
-                _integrand(psi[l], phi[l], integrand[l], bh, punct)
+                _integrand(psi[l], phi[l], integrand[l], bh, punct, mat, l)
             integral = geom.computeSum(integrand)
             bh["constant_K"] = -math.sqrt(abs(integral) / volume)
             res.constant_K.append(bh["constant_K"])
         for l in range(nlev):  # :154-160
-            _coefs(psi[l], phi[l], a[l], rhs[l], bh, punct)
+            _coefs(psi[l], phi[l], a[l], rhs[l], bh, punct, mat, l)
         amr = AMRSolver(list(zip(grids, a, b)), op_params, sp)  # :163-170
         solver = BiCGStabSolver(MultilevelLinearOp(amr, prm.numMGIterations),
                                 tolerance=prm.tolerance, max_iterations=prm.max_iterations,
@@ -259,7 +273,7 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
         def write():
             output_final_data(psi, bh, nlev - 1, refs,
                               os.path.join(output_dir, "vcPoissonFinal.3d.hdf5"), phi=phis,
-                              punctures=punct)
+                              punctures=punct, matter=mat)
     return finish_nl_loop(res, write)
 
 

@@ -14,7 +14,9 @@ phi_0 is evaluated in place too (the Gaussian of MyPhiFunction.H) unless the
 caller passes the stored field (`phi`, one LevelData per level; phi.py): then
 the "phi" / "phi_0" component is copied from it.  With `punctures` (a
 punctures.PunctureSet) the A_ij_0, A_ij and chi components come from the
-puncture table instead of the deck's two holes.
+puncture table instead of the deck's two holes.  With `matter` (matter.py)
+the final data's "Pi" component (26) is the stored Pi_0, as given; the solver
+data (the reference's multigrid_vars) has no Pi.
 """
 from __future__ import annotations
 
@@ -25,6 +27,7 @@ import numpy as np
 
 from ._lib import call, io_call
 from .core import BH_KEYS, LevelData
+from .matter import fill_matter, table_or_null
 from .punctures import table_args
 
 GRCHOMBO_VARS = (  # GRChomboUserVariables.hpp:58-75
@@ -50,13 +53,25 @@ def _enc(filename: Optional[str]):
 def output_final_data(psi: Sequence[LevelData], bh: dict, max_level: int = 0,
                       ref_ratio: Optional[Sequence[int]] = None,
                       filename: Optional[str] = None,
-                      phi: Optional[Sequence[LevelData]] = None, punctures=None) -> None:
+                      phi: Optional[Sequence[LevelData]] = None, punctures=None,
+                      matter=None) -> None:
     """output_final_data (WriteOutput.H:127-227); constant_K = bh['constant_K'].
     filename None: "vcPoissonFinal.3d.hdf5" in the working directory.
     phi: the stored phi_0 per level (None: the analytic Gaussian).
-    punctures: the puncture table (None: the deck's two holes)."""
+    punctures: the puncture table (None: the deck's two holes).
+    matter: a matter.Matter (None: today's calls, Pi = 0): the stored Pi_0 is
+    written as given into component 26, "Pi".  GRChombo calls Pi the "(minus)
+    conjugate momentum"; only Pi^2 enters the sources here, so its sign is the
+    caller's convention."""
     n = len(psi)
     rr = list(ref_ratio) if ref_ratio is not None else [2] * n
+    if matter is not None:
+        mat = fill_matter(matter, [f.grid for f in psi], bh, "output_final_data")
+        io_call("mgic_io_write_final_data_matter", _enc(filename), n, _handles(psi),
+                _handles(phi) if phi is not None else None, _bh(bh), *table_or_null(punctures),
+                _handles(mat.pi) if mat.pi is not None else None, mat.potential.pot(),
+                int(max_level), (ctypes.c_int * n)(*rr))
+        return
     if punctures is not None:
         io_call("mgic_io_write_final_data_punct", _enc(filename), n, _handles(psi),
                 _handles(phi) if phi is not None else None, _bh(bh), *table_args(punctures),
@@ -96,12 +111,15 @@ def output_solver_data(dpsi: Sequence[LevelData], rhs: Sequence[LevelData],
 
 def grchombo_vars(psi: LevelData, n: int, bh: dict, k0: int = 0, nk: Optional[int] = None,
                   out_device_ptr: Optional[int] = None,
-                  phi: Optional[LevelData] = None, punctures=None) -> Optional[np.ndarray]:
+                  phi: Optional[LevelData] = None, punctures=None,
+                  matter=None) -> Optional[np.ndarray]:
     """set_output_data for local box n, planes [k0, k0+nk): (31, nk, ny, nx) on
     the host, or written to device memory at out_device_ptr (returns None).
     phi: the stored phi_0 (None: the analytic Gaussian).
-    punctures: the puncture table (None: the deck's two holes)."""
-    return _vars(0, psi, None, None, n, bh, k0, nk, out_device_ptr, phi, punctures)
+    punctures: the puncture table (None: the deck's two holes).
+    matter: a matter.Matter (None: today's calls): component 26, "Pi", is its
+    stored Pi_0 as given (the sign is the caller's convention)."""
+    return _vars(0, psi, None, None, n, bh, k0, nk, out_device_ptr, phi, punctures, matter)
 
 
 def solver_vars(dpsi: LevelData, rhs: LevelData, psi: LevelData, n: int, bh: dict, k0: int = 0,
@@ -111,7 +129,7 @@ def solver_vars(dpsi: LevelData, rhs: LevelData, psi: LevelData, n: int, bh: dic
     return _vars(1, psi, dpsi, rhs, n, bh, k0, nk, out_device_ptr, phi, punctures)
 
 
-def _vars(kind, psi, dpsi, rhs, n, bh, k0, nk, dev, phi=None, punctures=None):
+def _vars(kind, psi, dpsi, rhs, n, bh, k0, nk, dev, phi=None, punctures=None, matter=None):
     lo, hi = psi.grid.local_box(n)[:3], psi.grid.local_box(n)[3:]
     nx, ny, nz = (hi[d] - lo[d] + 1 for d in range(3))
     nk = nz - k0 if nk is None else nk
@@ -122,7 +140,12 @@ def _vars(kind, psi, dpsi, rhs, n, bh, k0, nk, dev, phi=None, punctures=None):
         out = np.empty((nc, nk, ny, nx))
         ptr = out.ctypes.data_as(ctypes.c_void_p)
     hphi = phi.handle if phi is not None else None
-    if punctures is not None and kind == 0:
+    if matter is not None:  # kind 0 only
+        mat = fill_matter(matter, [psi.grid], bh, "grchombo_vars")
+        call("mgic_field_grchombo_vars_matter", psi.handle, hphi, n, k0, nk, _bh(bh),
+             *table_or_null(punctures), mat.pi[0].handle if mat.pi is not None else None,
+             mat.potential.pot(), ptr, int(dev is not None))
+    elif punctures is not None and kind == 0:
         call("mgic_field_grchombo_vars_punct", psi.handle, hphi, n, k0, nk, _bh(bh),
              *table_args(punctures), ptr, int(dev is not None))
     elif punctures is not None:

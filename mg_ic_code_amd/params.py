@@ -64,6 +64,10 @@ class PoissonParameters:
     # the optional puncture table (num_punctures, puncture1 .. punctureN): rows
     # of m x y z Px Py Pz Jx Jy Jz (punctures.py); None: the two holes above
     punctures: Optional[list] = None
+    # the optional matter keys (scalar_V0, scalar_mass, scalar_self_coupling,
+    # pi_amplitude: a constant Pi; matter.py): the keys the deck gives, by
+    # name; None: no matter
+    matter: Optional[dict] = None
 
     def bh(self, constant_K: float = 0.0) -> dict:
         """Inputs of set_a_coef / set_rhs (domain length of direction 0)."""
@@ -142,6 +146,12 @@ def read_params(text: str, overrides: Optional[Dict[str, str]] = None) -> Poisso
                                  f"got {len(kv[key])}")
             rows.append([float(x) for x in kv[key]])
         p.punctures = rows
+    # the matter keys (not keys of the reference): absent = nothing changes
+    matter = {k: get(k, float, required=False)
+              for k in ("scalar_V0", "scalar_mass", "scalar_self_coupling", "pi_amplitude")}
+    matter = {k: v for k, v in matter.items() if v is not None}
+    if matter:
+        p.matter = matter
     return p
 
 

@@ -17,9 +17,16 @@ With --puncture "m x y z Px Py Pz Jx Jy Jz" (repeatable, 1 to 8 times) the
 holes are that puncture table (mg_ic_code_amd/punctures.py) instead of the
 deck's two holes or the deck's own table (num_punctures, puncture1 ...).
 
+With --potential "V0 mass lambda" and/or --pi VALUE the scalar field's
+potential V = V0 + mass^2 phi^2 / 2 + lambda phi^4 / 4 and a constant velocity
+Pi enter the sources as rho = Pi^2 / 2 + V (mg_ic_code_amd/matter.py); either
+flag overrides the deck's scalar_V0, scalar_mass, scalar_self_coupling and
+pi_amplitude.
+
 usage: python tools/run_poisson.py [params.txt] [--size N] [--boxes-per-rank x,y,z]
                                    [--max-level K] [--phi gaussian|sine]
                                    [--puncture "m x y z Px Py Pz Jx Jy Jz"]...
+                                   [--potential "V0 mass lambda"] [--pi VALUE]
 """
 import argparse
 import json
@@ -44,6 +51,10 @@ def main():
     ap.add_argument("--puncture", action="append", default=None, metavar="ROW",
                     help="a Bowen-York puncture, \"m x y z Px Py Pz Jx Jy Jz\"; repeatable; "
                          "overrides the deck's table")
+    ap.add_argument("--potential", default=None, metavar="\"V0 MASS LAMBDA\"",
+                    help="the scalar potential's three coefficients; overrides the deck's")
+    ap.add_argument("--pi", type=float, default=None, metavar="VALUE",
+                    help="a constant field velocity Pi; overrides the deck's pi_amplitude")
     args = ap.parse_args()
     import mg_ic_code_amd as mg
     from mg_ic_code_amd.decomposition import decompose
@@ -63,15 +74,31 @@ def main():
     if punct is not None:
         for i, p in enumerate(punct):
             print(f"puncture {i + 1}: m {p.mass!r} at {p.position} P {p.momentum} J {p.spin}")
+    from mg_ic_code_amd.matter import Matter, PiProfile, ScalarPotential
+    matter = Matter.from_params(prm)
+    if args.potential is not None or args.pi is not None:
+        pot = matter.potential if matter is not None else ScalarPotential()
+        pi = matter.pi if matter is not None else None
+        if args.potential is not None:
+            coefs = args.potential.split()
+            if len(coefs) != 3:
+                ap.error("--potential needs three numbers: V0 mass lambda")
+            pot = ScalarPotential(*coefs)
+        if args.pi is not None:
+            pi = PiProfile.constant(args.pi)
+        matter = Matter(pot, pi)
+    if matter is not None:
+        print(f"matter: {matter.potential}, Pi {matter.pi.value if matter.pi else 0.0!r}")
     if args.max_level > 0:
         from mg_ic_code_amd.grids import set_grids
         levels = set_grids(grid.comm, prm, grid, max_level=args.max_level, phi0=phi0,
-                           punctures=punct)
+                           punctures=punct, matter=matter)
         for lev, g in enumerate(levels):
             cells = sum((b[3] - b[0] + 1) * (b[4] - b[1] + 1) * (b[5] - b[2] + 1) for b in g.boxes)
             print(f"level {lev}: {len(g.boxes)} boxes, {cells} cells")
     t0 = time.perf_counter()
-    res = poisson_solve(levels, prm, max_depth=args.max_depth, phi0=phi0, punctures=punct)
+    res = poisson_solve(levels, prm, max_depth=args.max_depth, phi0=phi0, punctures=punct,
+                        matter=matter)
     mg.device_synchronize()
     dt = time.perf_counter() - t0
     for i, (nrm, it) in enumerate(zip(res.dpsi_norms, res.linear_iterations)):
@@ -80,6 +107,13 @@ def main():
            "converged": res.converged, "seconds": round(dt, 3)}
     if punct is not None:
         out["punctures"] = [list(p.row()) for p in punct]
+    if matter is not None:
+        p = matter.potential
+        out["matter"] = {"V0": p.V0, "mass": p.mass, "self_coupling": p.self_coupling,
+                         "pi": matter.pi.value if matter.pi else 0.0}
+        out["dpsi_norms"] = res.dpsi_norms
+        out["linear_iterations"] = res.linear_iterations
+        out["constant_K"] = res.constant_K
     print(json.dumps(out))
 
 
