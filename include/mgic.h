@@ -542,8 +542,9 @@ MGIC_API int mgic_field_solver_vars_punct(mgic_field dpsi, mgic_field rhs, mgic_
  * holes of bh.  With pot all zero and pi NULL or zero they give the bits of
  * the entry points above.  MGIC_EBADARG, before anything is launched, for
  * what the _punct forms refuse, a non-finite pot entry and a pi of another
- * layout.  The momentum constraint's source Pi d_i phi is not solved for: as
- * with every A_ij input, that is the caller's responsibility. */
+ * layout.  The momentum constraint's source Pi d_i phi is not solved for, so
+ * data with a non-zero Pi and a varying phi_0 violate that constraint by
+ * 8 pi G Pi d_i phi; mgic_field_constraints (below) reports the violation. */
 MGIC_API int mgic_field_nl_coefs_matter(mgic_field psi, mgic_field phi, mgic_field acoef,
                                         mgic_field rhs, const double bh[13], int n,
                                         const double *table, mgic_field pi, const double pot[3]);
@@ -557,6 +558,44 @@ MGIC_API int mgic_field_grchombo_vars_matter(mgic_field psi, mgic_field phi, int
                                              const double bh[13], int npunct, const double *table,
                                              mgic_field pi, const double pot[3], double *out,
                                              int out_on_device);
+/* ---- Constraints: the Hamiltonian and momentum constraints of the data at
+ * psi (GRChombo's Constraints for a conformally flat metric and constant K,
+ * written in chi = psi_0^-4 and A~_ij = psi_0^-6 Abar_ij).  Per valid cell,
+ * with psi_0 = psi + psi_bh, K = constant_K and lap, rho_grad, A2, rho as
+ * mgic_field_nl_coefs* forms them:
+ *   m       = (2.0/3.0)*(K*K) - 16.0*M_PI*G*rho
+ *   Ham     = m - A2*pow(psi_0,-12.0) - 16.0*M_PI*G*rho_grad*pow(psi_0,-4.0)
+ *               - 8.0*lap*pow(psi_0,-5.0)
+ *   Ham_abs = the sum of the absolute values of (2/3)K^2, 16 pi G rho and the
+ *             three other terms of Ham (the scale a residual is judged by)
+ *   Mom_i   = pow(psi_0,-6.0) * sum_j 0.5/dx*(Abar_ij(iv+e_j) - Abar_ij(iv-e_j))
+ *               + 8.0*M_PI*G*Pi*(0.5/dx*(phi_0(iv+e_i) - phi_0(iv-e_i)))
+ * so Ham = (2/3) K^2 - (2/3) * (mgic_field_nl_integrand*'s value).  Abar_ij
+ * at the neighbouring cells is the analytic Bowen-York tensor evaluated at
+ * their centres: no ghost cell is read for it, and as it is divergence-free
+ * away from the punctures that term measures truncation.  psi and a stored
+ * phi are read with their first ghost layer as stored (the preconditions of
+ * the integrand); pi at valid cells only.  GRChombo's S_i is -Pi d_i phi: Pi
+ * enters with the sign it is stored with.
+ *
+ * Every optional source is nullable: phi NULL, the analytic Gaussian; table
+ * NULL with n = 0, the two holes of bh; pot NULL, no matter (the momentum
+ * source is the literal zero, and pi must be NULL); pi NULL, Pi = 0.
+ * mgic_field_constraints fills five fields on psi's layout, all required and
+ * distinct from each other and from the inputs.  mgic_field_constraint_vars
+ * gives Ham, Mom1, Mom2, Mom3 of planes [k0, k0 + nk) of local box `box` as
+ * (4, nk, ny, nx), the layout of components 27-30 of
+ * mgic_field_grchombo_vars*.  MGIC_EBADARG, before anything is launched, for
+ * what the _matter forms refuse, a NULL or foreign-layout output, aliased
+ * outputs and a pi without pot. */
+MGIC_API int mgic_field_constraints(mgic_field psi, mgic_field phi, mgic_field ham,
+                                    mgic_field mom1, mgic_field mom2, mgic_field mom3,
+                                    mgic_field ham_abs, const double bh[13], int n,
+                                    const double *table, mgic_field pi, const double *pot);
+MGIC_API int mgic_field_constraint_vars(mgic_field psi, mgic_field phi, int box, int k0, int nk,
+                                        const double bh[13], int npunct, const double *table,
+                                        mgic_field pi, const double *pot, double *out,
+                                        int out_on_device);
 /* the field's layout: domain, periodicity, dx, number of boxes (all ranks),
  * this rank and the job size; box i's extent, owner rank and local index
  * (-1 if not local); a barrier over the field's communicator */

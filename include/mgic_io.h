@@ -99,6 +99,23 @@ MGIC_IO_API int mgic_io_write_final_data_matter(const char *filename, int nlevel
                                                 const double pot[3], int max_level,
                                                 const int *ref_ratio);
 
+/* The final-data writer with the diagnostic components filled (mgic.h,
+ * "Constraints"): components 27-30 (Ham, Mom1, Mom2, Mom3) carry
+ * mgic_field_constraint_vars of the same sources instead of the zeros the
+ * writers above put there.  The arguments are those of
+ * mgic_io_write_final_data_matter, every optional one nullable: phi NULL (the
+ * analytic Gaussian), table NULL with npunct = 0 (the two holes of bh), pot
+ * NULL (no matter; pi must then be NULL), pi NULL (Pi = 0).  The other 27
+ * components and the file layout are what the writer above that takes the
+ * same sources produces.  What the _matter form refuses, and a pi without
+ * pot, are MGIC_EBADARG before the file is created. */
+MGIC_IO_API int mgic_io_write_final_data_constraints(const char *filename, int nlevels,
+                                                     const mgic_field *psi, const mgic_field *phi,
+                                                     const double bh[13], int npunct,
+                                                     const double *table, const mgic_field *pi,
+                                                     const double *pot, int max_level,
+                                                     const int *ref_ratio);
+
 /* The same two layouts from host arrays (tests, and callers whose data is
  * already on the host).  kind 0: final data (31 components), 1: solver data
  * (10).  Level l has nbox[l] boxes (6 ints each, all levels concatenated in

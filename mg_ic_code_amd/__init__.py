@@ -29,6 +29,13 @@ from .core import (  # noqa: F401
     set_nl_coefs,
     set_device,
 )
+from .constraints import (  # noqa: F401
+    ConstraintFields,
+    ConstraintReport,
+    constraint_vars,
+    constraints,
+    set_constraints,
+)
 from .grids import set_grids  # noqa: F401
 from ._lib import IO_LIB_PATH, LIB_PATH, lib  # noqa: F401
 from .matter import Matter, PiProfile, ScalarPotential  # noqa: F401

@@ -236,6 +236,9 @@ SIGNATURES = {
     "mgic_field_regrid_condition_matter": [H, H, H, PD, c_int, PD, H, PD],
     "mgic_field_grchombo_vars_matter": [H, H, c_int, c_int, c_int, PD, c_int, PD, H, PD, c_void_p,
                                         c_int],
+    "mgic_field_constraints": [H, H, H, H, H, H, H, PD, c_int, PD, H, PD],
+    "mgic_field_constraint_vars": [H, H, c_int, c_int, c_int, PD, c_int, PD, H, PD, c_void_p,
+                                   c_int],
     "mgic_field_layout": [H, PI, PI, PD, PI, PI, PI],
     "mgic_field_box": [H, c_int, PI, PI, PI],
     "mgic_field_barrier": [H],
@@ -344,6 +347,8 @@ IO_SIGNATURES = {
     "mgic_io_write_final_data_punct": [c_char_p, c_int, PH, PH, PD, c_int, PD, c_int, PI],
     "mgic_io_write_solver_data_punct": [c_char_p, c_int, PH, PH, PH, PH, PD, c_int, PD, PI, c_int],
     "mgic_io_write_final_data_matter": [c_char_p, c_int, PH, PH, PD, c_int, PD, PH, PD, c_int, PI],
+    "mgic_io_write_final_data_constraints": [c_char_p, c_int, PH, PH, PD, c_int, PD, PH, PD, c_int,
+                                             PI],
     "mgic_io_write_host": [c_char_p, c_int, c_int, PI, PI, PI, PD, PI, PD, c_int, c_int],
 }
 _io = None

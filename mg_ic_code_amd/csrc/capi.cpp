@@ -912,6 +912,107 @@ MGIC_API int mgic_field_grchombo_vars_matter(mgic_field psi, mgic_field phi, int
                      &c.m);
   });
 }
+// ---- the constraints of the data (mgic.h, "Constraints"): one entry point
+// per job, every optional source nullable.  table null with n = 0: the two
+// holes of bh; pot null: no matter (pi must then be null too); pi null: Pi = 0.
+// Everything is checked before the first launch.
+struct ConstraintCall {
+  kern::PunctureTable t;
+  const kern::PunctureTable *table = nullptr;
+  MatterCapi m;
+  const MatterCapi *matter = nullptr;
+};
+static void constraint_call(ConstraintCall &c, int n, const double *table, mgic_field pi,
+                            const double *pot) {
+  MGIC_CHECK(table || n == 0, "null argument: punctures (with a count that is not 0)");
+  if (table) {
+    kern::set_punctures(c.t, n, table);
+    c.table = &c.t;
+  }
+  MGIC_CHECK(pot || !pi, "pi without pot: the matter's potential is required with its Pi_0");
+  if (pot) {
+    c.m.terms = kern::MatterTerms{pot[0], pot[1], pot[2], nullptr};
+    kern::check_matter(c.m.terms);
+    c.m.pi = pi;
+    c.matter = &c.m;
+  }
+}
+MGIC_API int mgic_field_constraints(mgic_field psi, mgic_field phi, mgic_field ham,
+                                    mgic_field mom1, mgic_field mom2, mgic_field mom3,
+                                    mgic_field ham_abs, const double bh[13], int n,
+                                    const double *table, mgic_field pi, const double *pot) {
+  return guard([&] {
+    ConstraintCall c;
+    constraint_call(c, n, table, pi, pot);
+    NEED(psi);
+    NEED(ham);
+    NEED(mom1);
+    NEED(mom2);
+    NEED(mom3);
+    NEED(ham_abs);
+    NEED(bh);
+    const Grid &g = *psi->f->grid;
+    const mgic_field out[5] = {ham, mom1, mom2, mom3, ham_abs};
+    static const char *const names[5] = {"ham", "mom1", "mom2", "mom3", "ham_abs"};
+    for (int a = 0; a < 5; ++a) {
+      check_same_layout(g, *out[a]->f, names[a]);
+      MGIC_CHECK(out[a]->f != psi->f && (!phi || out[a]->f != phi->f) &&
+                     (!pi || out[a]->f != pi->f),
+                 std::string("aliased argument: ") + names[a] + " is an input");
+      for (int b = 0; b < a; ++b)
+        MGIC_CHECK(out[a]->f != out[b]->f,
+                   std::string("aliased argument: ") + names[a] + " is " + names[b]);
+    }
+    if (phi) check_same_layout(g, *phi->f, "phi");
+    check_matter_layout(g, c.matter);
+    const kern::BhParams p = bh_params(bh);
+    kern::MatterTerms mt;
+    for (int b = 0; b < g.nlocal(); ++b) {
+      const BoxArgs a = g.box_args_plain(b);
+      kern::ConstraintOut o;
+      for (int q = 0; q < 5; ++q) o.c[q] = out[q]->f->p[b];
+      o.sy = a.sy;
+      o.sz = a.sz;
+      kern::constraints(o, psi->f->p[b], phi ? phi->f->p[b] : nullptr, a, 0, a.nz, g.dx, p,
+                        g.comm->stream(), c.table, box_matter(c.matter, b, mt));
+    }
+  });
+}
+MGIC_API int mgic_field_constraint_vars(mgic_field psi, mgic_field phi, int box, int k0, int nk,
+                                        const double bh[13], int npunct, const double *table,
+                                        mgic_field pi, const double *pot, double *out,
+                                        int out_on_device) {
+  return guard([&] {
+    ConstraintCall c;
+    constraint_call(c, npunct, table, pi, pot);
+    NEED(psi);
+    NEED(bh);
+    NEED(out);
+    const Grid &g = *psi->f->grid;
+    if (phi) check_same_layout(g, *phi->f, "phi");
+    check_matter_layout(g, c.matter);
+    MGIC_CHECK(box >= 0 && box < g.nlocal(), "bad local box index");
+    const FabGeom &fg = g.geom[box];
+    MGIC_CHECK(k0 >= 0 && nk >= 1 && k0 + nk <= fg.nz, "plane range outside the box");
+    const long V = (long)fg.nx * fg.ny * nk;
+    const size_t bytes = sizeof(double) * 4 * (size_t)V;
+    const hipStream_t st = g.comm->stream();
+    double *d = out;
+    if (!out_on_device) d = static_cast<double *>(scratch_device(bytes));
+    kern::ConstraintOut o;
+    for (int q = 0; q < 4; ++q) o.c[q] = d + q * V;
+    o.c[4] = nullptr;
+    o.sy = fg.nx;
+    o.sz = (long)fg.nx * fg.ny;
+    kern::MatterTerms mt;
+    kern::constraints(o, psi->f->p[box], phi ? phi->f->p[box] : nullptr, g.box_args_plain(box), k0,
+                      nk, g.dx, bh_params(bh), st, c.table, box_matter(c.matter, box, mt));
+    if (!out_on_device) {
+      MGIC_HIP(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, st));
+      MGIC_HIP(hipStreamSynchronize(st));
+    }
+  });
+}
 MGIC_API int mgic_field_norm(mgic_field x, int ord, double *out) {
   return guard([&] {
     NEED(x);

@@ -250,7 +250,8 @@ struct DataWriter {
 // the device path: layouts from the fields, rank 0 creates, ranks write
 // their boxes in turn
 void write_fields(const std::string &fname, Job &J, const std::vector<mgic_field> &lead,
-                  const std::function<void(int l, int n, int k0, int nk, double *)> &produce) {
+                  const std::function<void(int l, int n, int k0, int nk, long long plane, double *)>
+                      &produce) {  // plane: cells of one z-plane of box n
   const int nlev = (int)lead.size();
   int rank = 0, size = 1;
   J.levels.resize(nlev);
@@ -322,7 +323,7 @@ void write_fields(const std::string &fname, Job &J, const std::vector<mgic_field
                 host[cur].reserve((size_t)J.ncomp * plane * nk);
               }
               double *buf = host[cur].p;
-              produce(l, loc, k0, kk, buf);
+              produce(l, loc, k0, kk, plane, buf);
               join();
               const int ncomp = J.ncomp;
               writer = std::thread([&W, &werr, l, off, nc, k0, kk, plane, ncomp, buf] {
@@ -380,10 +381,13 @@ namespace {
 // the library checks it at the first box, before it launches anything
 // pot: null (today's components), or V0, mass, lambda with pi null (Pi = 0)
 // or one stored Pi_0 field per level, which becomes the component "Pi"
+// constraints: components 27-30 from mgic_field_constraint_vars (a second
+// small launch per slab) instead of set_output_data's zeros
 int write_final_data(const char *filename, int nlevels, const mgic_field *psi,
                      const mgic_field *phi, const double bh[13], int max_level,
                      const int *ref_ratio, int npunct = 0, const double *table = nullptr,
-                     const mgic_field *pi = nullptr, const double *pot = nullptr) {
+                     const mgic_field *pi = nullptr, const double *pot = nullptr,
+                     bool constraints = false) {
   return guard([&] {
     need(psi, "psi");
     need(bh, "bh");
@@ -398,7 +402,7 @@ int write_final_data(const char *filename, int nlevels, const mgic_field *psi,
     for (auto f : lead) need(f, "psi[l]");
     for (int l = 0; phi && l < nlevels; ++l) need(phi[l], "phi[l]");
     write_fields(filename ? filename : "vcPoissonFinal.3d.hdf5", J, lead,
-                 [&](int l, int n, int k0, int nk, double *out) {
+                 [&](int l, int n, int k0, int nk, long long plane, double *out) {
                    if (pot)
                      mg(mgic_field_grchombo_vars_matter(psi[l], phi ? phi[l] : nullptr, n, k0, nk,
                                                         bh, npunct, table, pi ? pi[l] : nullptr,
@@ -410,6 +414,10 @@ int write_final_data(const char *filename, int nlevels, const mgic_field *psi,
                      mg(mgic_field_grchombo_vars_phi(psi[l], phi[l], n, k0, nk, bh, out, 0));
                    else
                      mg(mgic_field_grchombo_vars(psi[l], n, k0, nk, bh, out, 0));
+                   if (constraints)  // Ham, Mom1..3: the slab's last four components
+                     mg(mgic_field_constraint_vars(psi[l], phi ? phi[l] : nullptr, n, k0, nk, bh,
+                                                   npunct, table, pi ? pi[l] : nullptr, pot,
+                                                   out + 27 * plane * nk, 0));
                  });
   });
 }
@@ -439,7 +447,8 @@ int write_solver_data(const char *filename, int nlevels, const mgic_field *dpsi,
     }
     char name[64];
     std::snprintf(name, sizeof name, "vcPoissonOut.3d_%d.hdf5", iter);  // WriteOutput.H:63-70
-    write_fields(filename ? filename : name, J, lead, [&](int l, int n, int k0, int nk, double *out) {
+    write_fields(filename ? filename : name, J, lead, [&](int l, int n, int k0, int nk, long long,
+                                                          double *out) {
       if (table)
         mg(mgic_field_solver_vars_punct(dpsi[l], rhs[l], psi[l], phi ? phi[l] : nullptr, n, k0, nk,
                                         bh, npunct, table, out, 0));
@@ -549,6 +558,32 @@ MGIC_IO_API int mgic_io_write_final_data_matter(const char *filename, int nlevel
   if (st != MGIC_OK) return st;
   return write_final_data(filename, nlevels, psi, phi, bh, max_level, ref_ratio, npunct, table, pi,
                           pot);
+}
+
+// the _matter form's checks with pot nullable (no matter: pi must be null too)
+MGIC_IO_API int mgic_io_write_final_data_constraints(const char *filename, int nlevels,
+                                                     const mgic_field *psi, const mgic_field *phi,
+                                                     const double bh[13], int npunct,
+                                                     const double *table, const mgic_field *pi,
+                                                     const double *pot, int max_level,
+                                                     const int *ref_ratio) {
+  const int st = guard([&] {
+    if (table || npunct != 0) check_punctures(npunct, table);
+    if (!pot && pi) throw IoError(MGIC_EBADARG, "pi without pot");
+    for (int c = 0; pot && c < 3; ++c)
+      if (!std::isfinite(pot[c]))
+        throw IoError(MGIC_EBADARG, "potential coefficients (V0, mass, lambda) must be finite");
+    need(psi, "psi");
+    if (nlevels < 1) throw IoError(MGIC_EBADARG, "nlevels < 1");
+    for (int l = 0; pi && l < nlevels; ++l) {
+      need(psi[l], "psi[l]");
+      need(pi[l], "pi[l]");
+      check_pi_layout(psi[l], pi[l]);
+    }
+  });
+  if (st != MGIC_OK) return st;
+  return write_final_data(filename, nlevels, psi, phi, bh, max_level, ref_ratio, npunct, table, pi,
+                          pot, true);
 }
 
 MGIC_IO_API int mgic_io_write_solver_data_punct(const char *filename, int nlevels,

@@ -993,14 +993,19 @@ __device__ __forceinline__ BhBowenYork bh_terms(const BhParams &p, const Punctur
   }
 }
 
-// GETRHOGRADPHIF (SetLevelDataF.ChF:65-103) of a stored field at one cell,
-// the field's ghost layer read as is
+// GETRHOGRADPHIF's centred difference of a stored field along the direction
+// of stride st (SetLevelDataF.ChF:84-92), the field's ghost layer read as is
+__device__ __forceinline__ double phi_dphidx(const double *__restrict__ phi, long idx, long st,
+                                             double dx) {
+  return 0.5 / dx * (+phi[idx + st] - phi[idx - st]);
+}
+// GETRHOGRADPHIF (SetLevelDataF.ChF:65-103) of a stored field at one cell
 __device__ __forceinline__ double phi_rho_grad(const double *__restrict__ phi, long idx,
                                                const BoxArgs &g, double dx) {
   const long st[3] = {1, g.sy, g.sz};
   double acc = 0.0;
   for (int d0 = 0; d0 < 3; ++d0) {
-    const double dphidx = 0.5 / dx * (+phi[idx + st[d0]] - phi[idx - st[d0]]);
+    const double dphidx = phi_dphidx(phi, idx, st[d0], dx);
     acc = acc + 0.5 * dphidx * dphidx;
   }
   return acc;
@@ -1019,6 +1024,26 @@ __device__ __forceinline__ double bh_phi0(const BhParams &p, const double *__res
                   bh_loc(iv[2], dx, p.domlen[2]));
   }
 }
+// the centred difference of phi_0 along direction d0 (stride st of a stored
+// field): the dphidx of GETRHOGRADPHIF, for the generators that need it per
+// direction.  bh_rho_grad's analytic branch keeps its own loop with the same
+// expression: routing it through here changes the register allocation of
+// every analytic instantiation of the existing generators.
+template <bool STORED>
+__device__ __forceinline__ double bh_dphidx(const BhParams &p, const double *__restrict__ phi,
+                                            const int iv[3], long idx, long st, double dx,
+                                            int d0) {
+  if constexpr (STORED) {
+    return phi_dphidx(phi, idx, st, dx);
+  } else {
+    double lp[3], lm[3];
+    for (int d = 0; d < 3; ++d) {
+      lp[d] = bh_loc(iv[d] + (d == d0), dx, p.domlen[d]);
+      lm[d] = bh_loc(iv[d] - (d == d0), dx, p.domlen[d]);
+    }
+    return 0.5 / dx * (+bh_phi(p, lp[0], lp[1], lp[2]) - bh_phi(p, lm[0], lm[1], lm[2]));
+  }
+}
 // rho_grad of phi_0: GETRHOGRADPHIF, SetLevelDataF.ChF:65-103
 template <bool STORED>
 __device__ __forceinline__ double bh_rho_grad(const BhParams &p, const double *__restrict__ phi,
@@ -1028,7 +1053,7 @@ __device__ __forceinline__ double bh_rho_grad(const BhParams &p, const double *_
     return phi_rho_grad(phi, idx, g, dx);
   } else {
     double rho_grad = 0.0;
-    for (int d0 = 0; d0 < 3; ++d0) {
+    for (int d0 = 0; d0 < 3; ++d0) {  // bh_dphidx's expression, kept in place
       double lp[3], lm[3];
       for (int d = 0; d < 3; ++d) {
         lp[d] = bh_loc(iv[d] + (d == d0), dx, p.domlen[d]);
@@ -1286,6 +1311,119 @@ __global__ __launch_bounds__(256) void k_output_vars(double *__restrict__ out,
   v[13] = b.A33 * factor;
 #pragma unroll
   for (int c = 0; c < 31; ++c) o[c * V] = v[c];
+}
+
+// ---- the constraints of the data (GRChombo's Constraints for a conformally
+// flat metric and constant K, in chi = psi_0^-4, A~_ij = psi_0^-6 Abar_ij):
+//   Ham   = m - A2 psi_0^-12 - 16 pi G rho_grad psi_0^-4 - 8 lap psi_0^-5
+//           (R = -8 psi_0^-5 lap; m = set_m_value at K = constant_K), so
+//           Ham = (2/3) K^2 - (2/3) * k_binary_bh<INTEGRAND>'s value
+//   Mom_i = psi_0^-6 d_j Abar_ij + 8 pi G Pi d_i phi   (S_i = -Pi d_i phi)
+//   Ham_abs: the sum of the absolute values of Ham's five terms
+// lap, rho_grad, A2, rho and psi_0 are k_binary_bh's.  d_j Abar_ij is the
+// centred difference of the analytic Bowen-York tensor evaluated at the six
+// neighbouring cell centres (no ghost cell of anything is read for it); d_i phi
+// is the difference inside GETRHOGRADPHIF (bh_dphidx).  psi and a stored phi
+// are read with their first ghost layer as stored, Pi at the cell alone.
+struct ConstraintCell {
+  double ham, mom[3], ham_abs;
+};
+// A_ij of the Bowen-York terms (selects, no register array)
+__device__ __forceinline__ double bh_A(const BhBowenYork &c, int i, int j) {
+  const int s = i + j;
+  if (i == j) return i == 0 ? c.A11 : i == 1 ? c.A22 : c.A33;
+  return s == 1 ? c.A12 : s == 2 ? c.A13 : c.A23;
+}
+template <bool STORED, bool TABLE, bool MATTER>
+__device__ __forceinline__ ConstraintCell bh_constraints(
+    const double *__restrict__ psi, const double *__restrict__ phi, const int iv[3], long idx,
+    const BoxArgs &g, double dx, const BhParams &p, const PunctureArg<TABLE> &t,
+    const MatterArg<MATTER> &mt) {
+  const long st[3] = {1, g.sy, g.sz};
+  ConstraintCell o;
+  const double psi_c = psi[idx];
+  double psi_0, A2;
+  {
+    const BhBowenYork c = bh_terms<TABLE>(p, t, iv, dx);
+    A2 = bh_A2(c);
+    psi_0 = psi_c + c.psi_bh;
+  }
+  double rho_grad = 0.0, dphi[3];
+#pragma unroll
+  for (int d0 = 0; d0 < 3; ++d0) {
+    dphi[d0] = bh_dphidx<STORED>(p, phi, iv, idx, st[d0], dx, d0);
+    rho_grad = rho_grad + 0.5 * dphi[d0] * dphi[d0];
+  }
+  const double rho = bh_rho<MATTER>(mt, bh_rho_phi0<MATTER, STORED>(p, phi, iv, idx, dx), idx);
+  double lap = 0.0;
+#pragma unroll
+  for (int d0 = 0; d0 < 3; ++d0)
+    lap = lap + 1.0 / dx / dx * (+1.0 * psi[idx - st[d0]] - 2.0 * psi_c + 1.0 * psi[idx + st[d0]]);
+  const double K = p.constant_K;
+  const double m_K = (2.0 / 3.0) * (K * K), m_rho = 16.0 * M_PI * p.G_Newton * rho;
+  const double m = m_K - m_rho;  // set_m_value
+  const double t_A = A2 * pow(psi_0, -12.0);
+  const double t_grad = 16.0 * M_PI * p.G_Newton * rho_grad * pow(psi_0, -4.0);
+  const double t_lap = 8.0 * lap * pow(psi_0, -5.0);
+  o.ham = m - t_A - t_grad - t_lap;
+  o.ham_abs = fabs(m_K) + fabs(m_rho) + fabs(t_A) + fabs(t_grad) + fabs(t_lap);
+  // d_j Abar_ij, one pair of neighbours at a time.  The loop over j stays
+  // rolled: unrolled, the six inlined Bowen-York evaluations take the deck
+  // instantiations to 266 VGPRs (one wave per SIMD, AGPR spills); rolled, every
+  // instantiation stays below 168 (three waves), and bh_A selects by j
+  double divA[3] = {0.0, 0.0, 0.0};
+#pragma unroll 1
+  for (int j = 0; j < 3; ++j) {
+    const int ip[3] = {iv[0] + (j == 0), iv[1] + (j == 1), iv[2] + (j == 2)};
+    const int im[3] = {iv[0] - (j == 0), iv[1] - (j == 1), iv[2] - (j == 2)};
+    double Ap[3];
+    {
+      const BhBowenYork c = bh_terms<TABLE>(p, t, ip, dx);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) Ap[i] = bh_A(c, i, j);
+    }
+    const BhBowenYork c = bh_terms<TABLE>(p, t, im, dx);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) divA[i] = divA[i] + 0.5 / dx * (Ap[i] - bh_A(c, i, j));
+  }
+  const double w = pow(psi_0, -6.0);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    if constexpr (MATTER) {
+      const double Pi_field = mt.m.pi ? mt.m.pi[idx] : 0.0;
+      o.mom[i] = w * divA[i] + 8.0 * M_PI * p.G_Newton * Pi_field * dphi[i];
+    } else {
+      o.mom[i] = w * divA[i] + 0.0;  // no matter: the literal zero, as bh_rho
+    }
+  }
+  return o;
+}
+// where k_constraints writes: component c of cell (i, j, k) of the launch at
+// c[c][i + j * sy + k * sz].  The five fields of a box (Ham, Mom1..3, Ham_abs
+// on the box's strides), or components of a slab (c[4] null: no Ham_abs)
+// One thread per cell of planes [k0, k0 + nk) of the box, TX x TY tiles.
+// STORED / TABLE / MATTER as in k_binary_bh.
+template <bool STORED, bool TABLE, bool MATTER>
+__global__ __launch_bounds__(256) void k_constraints(const ConstraintOut o,
+                                                     const double *__restrict__ psi,
+                                                     const double *__restrict__ phi,
+                                                     const BoxArgs g, int k0, double dx,
+                                                     const BhParams p,
+                                                     const PunctureArg<TABLE> t,
+                                                     const MatterArg<MATTER> mt) {
+  const int i = blockIdx.x * TX + threadIdx.x;
+  const int j = blockIdx.y * TY + threadIdx.y;
+  const int k = blockIdx.z;
+  if (i >= g.nx || j >= g.ny) return;
+  const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k0 + k};
+  const long idx = (long)i + (long)j * g.sy + (long)(k0 + k) * g.sz;
+  const ConstraintCell c = bh_constraints<STORED, TABLE, MATTER>(psi, phi, iv, idx, g, dx, p, t, mt);
+  const long oi = (long)i + (long)j * o.sy + (long)k * o.sz;
+  o.c[0][oi] = c.ham;
+  o.c[1][oi] = c.mom[0];
+  o.c[2][oi] = c.mom[1];
+  o.c[3][oi] = c.mom[2];
+  if (o.c[4]) o.c[4][oi] = c.ham_abs;
 }
 
 // ---- phi_0 as a stored field (the c_phi_0 component set_initial_conditions
@@ -2344,6 +2482,44 @@ void output_vars(int kind, double *out, const double *psi, const double *dpsi, c
   else  // the solver data has no Pi
     launch_output_vars<1, false>(out, psi, dpsi, rhs, phi, g, k0, nk, dx, p, table, none, st);
   check_launch();
+}
+
+template <bool MATTER>
+static void launch_constraints(const ConstraintOut &o, const double *psi, const double *phi,
+                               const BoxArgs &g, int k0, int nk, double dx, const BhParams &p,
+                               const PunctureTable *t, const MatterArg<MATTER> &m,
+                               hipStream_t st) {
+  const dim3 grid = grid_cells(g.nx, g.ny, nk);
+  const PunctureArg<false> none;
+  if (t && phi)
+    k_constraints<true, true, MATTER><<<grid, kBlock, 0, st>>>(o, psi, phi, g, k0, dx, p,
+                                                               table_arg(t), m);
+  else if (t)
+    k_constraints<false, true, MATTER><<<grid, kBlock, 0, st>>>(o, psi, nullptr, g, k0, dx, p,
+                                                                table_arg(t), m);
+  else if (phi)
+    k_constraints<true, false, MATTER><<<grid, kBlock, 0, st>>>(o, psi, phi, g, k0, dx, p, none,
+                                                                m);
+  else
+    k_constraints<false, false, MATTER><<<grid, kBlock, 0, st>>>(o, psi, nullptr, g, k0, dx, p,
+                                                                 none, m);
+  check_launch();
+}
+
+void constraints(const ConstraintOut &o, const double *psi, const double *phi, const BoxArgs &g,
+                 int k0, int nk, double dx, const BhParams &p, hipStream_t st,
+                 const PunctureTable *table, const MatterTerms *matter) {
+  check_table(table);
+  if (matter) check_matter(*matter);
+  if (!psi) throw Error(kBadArg, "null argument: psi");
+  for (int c = 0; c < 4; ++c)
+    if (!o.c[c]) throw Error(kBadArg, "null argument: constraint output");
+  if (k0 < 0 || k0 + nk > g.nz) throw Error(kBadArg, "plane range outside the box");
+  if (g.nx <= 0 || g.ny <= 0 || nk <= 0) return;
+  if (matter)
+    launch_constraints<true>(o, psi, phi, g, k0, nk, dx, p, table, matter_arg(matter), st);
+  else
+    launch_constraints<false>(o, psi, phi, g, k0, nk, dx, p, table, MatterArg<false>(), st);
 }
 
 void fill_phi(int profile, double *phi, const BoxArgs &g, double dx, const BhParams &p,

@@ -269,6 +269,23 @@ void output_vars(int kind, double *out, const double *psi, const double *dpsi, c
                  const double *phi, const BoxArgs &g, int k0, int nk, double dx, const BhParams &p,
                  hipStream_t st, const PunctureTable *table = nullptr,
                  const MatterTerms *matter = nullptr);
+// The Hamiltonian and momentum constraints of the data at psi (GRChombo's
+// Constraints for a conformally flat metric and constant K; kernels.hip
+// bh_constraints) for planes [k0, k0 + nk) of a valid box.  Component c (Ham,
+// Mom1, Mom2, Mom3, Ham_abs) of cell (i, j, k0 + k) goes to
+// c[c][i + j * sy + k * sz]: the five fields of the box (their pointers and
+// strides, k0 = 0), or four components of an output slab (c[4] null: Ham_abs
+// is not written).  psi (required) and a stored phi are read with their first
+// ghost layer as stored; the Bowen-York terms at the neighbouring cells are
+// evaluated in place.  matter nullptr: the momentum source is the literal
+// zero; its pi (valid cells only) enters Mom_i with the sign it is stored with.
+struct ConstraintOut {
+  double *c[5];
+  long sy, sz;
+};
+void constraints(const ConstraintOut &o, const double *psi, const double *phi, const BoxArgs &g,
+                 int k0, int nk, double dx, const BhParams &p, hipStream_t st,
+                 const PunctureTable *table = nullptr, const MatterTerms *matter = nullptr);
 // ---- phi_0 as a stored field (SetLevelData.cpp:32-71's c_phi_0): the profile
 // at every cell centre of the box grown by one, for the generators' `phi`
 enum PhiProfile { kPhiGaussian = 0, kPhiSine = 1 };  // MyPhiFunction.H:14-15, :18-20

@@ -45,6 +45,7 @@ import os
 from .core import (AMRMultiGrid, AMRSolver, BiCGStabSolver, Grid, LevelData, MultilevelLinearOp,
                    OperatorParams, SolverParams, defineOperatorFactory, set_nl_coefs, BH_KEYS)
 from ._lib import call
+from .constraints import constraints as constraint_report
 from .output import output_final_data, output_solver_data
 from .matter import fill_matter, set_nl_coefs_matter, set_nl_integrand_matter
 from .params import PoissonParameters
@@ -74,6 +75,7 @@ class NLResult:
     linear_iterations: List[int] = field(default_factory=list)
     converged: bool = False
     constant_K: List[float] = field(default_factory=list)
+    constraints: object = None  # constraints.ConstraintReport (poisson_solve(constraints=True))
 
 
 def set_nl_integrand(psi: LevelData, out: LevelData, bh: dict) -> None:
@@ -111,7 +113,7 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
                   prolong_type: int = 1, bottom_solver: int = 1,
                   max_NL_iterations: Optional[int] = None,
                   output_dir: Optional[str] = None, phi0=None, punctures=None,
-                  matter=None) -> NLResult:
+                  matter=None, constraints: bool = False) -> NLResult:
     """phi0: None -- the analytic Gaussian, evaluated in the kernels; else a
     phi.PhiProfile, or one pre-filled LevelData per level: phi_0 is stored once
     before the NL loop (set_initial_conditions, SetLevelData.cpp:32-71) and the
@@ -123,12 +125,17 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
     matter: None -- the deck's (prm.matter) if it has one, else no matter
     (rho = 0, today's calls); else a matter.Matter: rho = 0.5 Pi^2 + V(phi_0)
     enters m in the coefficients and the K integrand, Pi_0 is stored once
-    before the NL loop, and the final data carry it as "Pi"."""
+    before the NL loop, and the final data carry it as "Pi".
+    constraints: True -- the Hamiltonian and momentum constraints of the
+    returned psi (constraints.py), with the solve's own sources and its last K,
+    are attached as NLResult.constraints, and the final data carry them in
+    components 27-30.  The solve itself is unchanged."""
     punct = resolve_punctures(punctures, prm)
     if isinstance(grid, (list, tuple)):
         if len(grid) > 1:
             return _poisson_solve_amr(list(grid), prm, max_depth, prolong_type, bottom_solver,
-                                      max_NL_iterations, output_dir, phi0, punct, matter)
+                                      max_NL_iterations, output_dir, phi0, punct, matter,
+                                      constraints)
         grid = grid[0]
     mat = fill_matter(matter, [grid], prm)
     phis = resolve_phi0(phi0, [grid], prm)
@@ -193,8 +200,11 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
         def write():
             output_final_data([psi], bh, prm.max_level, [2],
                               os.path.join(output_dir, "vcPoissonFinal.3d.hdf5"), phi=phis,
-                              punctures=punct, matter=mat)
-    return finish_nl_loop(res, write)
+                              punctures=punct, matter=mat, constraints=constraints)
+    finish_nl_loop(res, write)
+    if constraints:
+        res.constraints = constraint_report(psi, bh, phis, punct, mat)
+    return res
 
 
 def _op_params(prm: PoissonParameters, prolong_type: int) -> OperatorParams:
@@ -207,7 +217,7 @@ def _op_params(prm: PoissonParameters, prolong_type: int) -> OperatorParams:
 def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int,
                        prolong_type: int, bottom_solver: int, max_NL_iterations: Optional[int],
                        output_dir: Optional[str], phi0=None, punct=None,
-                       matter=None) -> NLResult:
+                       matter=None, constraints: bool = False) -> NLResult:
     """poissonSolve over nlevels = len(grids) AMR levels (Main_PoissonSolver.cpp:51-250)."""
     periodic = bool(prm.is_periodic)
     if periodic != all(grids[0].periodic):
@@ -273,8 +283,11 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
         def write():
             output_final_data(psi, bh, nlev - 1, refs,
                               os.path.join(output_dir, "vcPoissonFinal.3d.hdf5"), phi=phis,
-                              punctures=punct, matter=mat)
-    return finish_nl_loop(res, write)
+                              punctures=punct, matter=mat, constraints=constraints)
+    finish_nl_loop(res, write)
+    if constraints:
+        res.constraints = constraint_report(psi, bh, phis, punct, mat)
+    return res
 
 
 def finish_nl_loop(res: NLResult, write_final=None) -> NLResult:

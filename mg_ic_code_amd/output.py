@@ -54,7 +54,7 @@ def output_final_data(psi: Sequence[LevelData], bh: dict, max_level: int = 0,
                       ref_ratio: Optional[Sequence[int]] = None,
                       filename: Optional[str] = None,
                       phi: Optional[Sequence[LevelData]] = None, punctures=None,
-                      matter=None) -> None:
+                      matter=None, constraints: bool = False) -> None:
     """output_final_data (WriteOutput.H:127-227); constant_K = bh['constant_K'].
     filename None: "vcPoissonFinal.3d.hdf5" in the working directory.
     phi: the stored phi_0 per level (None: the analytic Gaussian).
@@ -62,9 +62,22 @@ def output_final_data(psi: Sequence[LevelData], bh: dict, max_level: int = 0,
     matter: a matter.Matter (None: today's calls, Pi = 0): the stored Pi_0 is
     written as given into component 26, "Pi".  GRChombo calls Pi the "(minus)
     conjugate momentum"; only Pi^2 enters the sources here, so its sign is the
-    caller's convention."""
+    caller's convention.
+    constraints: components 27-30 (Ham, Mom1..3) carry the constraints of the
+    data (constraints.py; Pi enters Mom_i with the sign it is stored with)
+    instead of set_output_data's zeros; nothing else in the file changes."""
     n = len(psi)
     rr = list(ref_ratio) if ref_ratio is not None else [2] * n
+    if constraints:
+        mat = None
+        if matter is not None:
+            mat = fill_matter(matter, [f.grid for f in psi], bh, "output_final_data")
+        io_call("mgic_io_write_final_data_constraints", _enc(filename), n, _handles(psi),
+                _handles(phi) if phi is not None else None, _bh(bh), *table_or_null(punctures),
+                _handles(mat.pi) if mat is not None and mat.pi is not None else None,
+                mat.potential.pot() if mat is not None else None, int(max_level),
+                (ctypes.c_int * n)(*rr))
+        return
     if matter is not None:
         mat = fill_matter(matter, [f.grid for f in psi], bh, "output_final_data")
         io_call("mgic_io_write_final_data_matter", _enc(filename), n, _handles(psi),
@@ -112,14 +125,17 @@ def output_solver_data(dpsi: Sequence[LevelData], rhs: Sequence[LevelData],
 def grchombo_vars(psi: LevelData, n: int, bh: dict, k0: int = 0, nk: Optional[int] = None,
                   out_device_ptr: Optional[int] = None,
                   phi: Optional[LevelData] = None, punctures=None,
-                  matter=None) -> Optional[np.ndarray]:
+                  matter=None, constraints: bool = False) -> Optional[np.ndarray]:
     """set_output_data for local box n, planes [k0, k0+nk): (31, nk, ny, nx) on
     the host, or written to device memory at out_device_ptr (returns None).
     phi: the stored phi_0 (None: the analytic Gaussian).
     punctures: the puncture table (None: the deck's two holes).
     matter: a matter.Matter (None: today's calls): component 26, "Pi", is its
-    stored Pi_0 as given (the sign is the caller's convention)."""
-    return _vars(0, psi, None, None, n, bh, k0, nk, out_device_ptr, phi, punctures, matter)
+    stored Pi_0 as given (the sign is the caller's convention).
+    constraints: components 27-30 (Ham, Mom1..3) are filled by a second launch
+    into the same array (constraints.py) instead of left at zero."""
+    return _vars(0, psi, None, None, n, bh, k0, nk, out_device_ptr, phi, punctures, matter,
+                 constraints)
 
 
 def solver_vars(dpsi: LevelData, rhs: LevelData, psi: LevelData, n: int, bh: dict, k0: int = 0,
@@ -129,7 +145,8 @@ def solver_vars(dpsi: LevelData, rhs: LevelData, psi: LevelData, n: int, bh: dic
     return _vars(1, psi, dpsi, rhs, n, bh, k0, nk, out_device_ptr, phi, punctures)
 
 
-def _vars(kind, psi, dpsi, rhs, n, bh, k0, nk, dev, phi=None, punctures=None, matter=None):
+def _vars(kind, psi, dpsi, rhs, n, bh, k0, nk, dev, phi=None, punctures=None, matter=None,
+          constraints=False):
     lo, hi = psi.grid.local_box(n)[:3], psi.grid.local_box(n)[3:]
     nx, ny, nz = (hi[d] - lo[d] + 1 for d in range(3))
     nk = nz - k0 if nk is None else nk
@@ -140,6 +157,7 @@ def _vars(kind, psi, dpsi, rhs, n, bh, k0, nk, dev, phi=None, punctures=None, ma
         out = np.empty((nc, nk, ny, nx))
         ptr = out.ctypes.data_as(ctypes.c_void_p)
     hphi = phi.handle if phi is not None else None
+    mat = None
     if matter is not None:  # kind 0 only
         mat = fill_matter(matter, [psi.grid], bh, "grchombo_vars")
         call("mgic_field_grchombo_vars_matter", psi.handle, hphi, n, k0, nk, _bh(bh),
@@ -162,6 +180,13 @@ def _vars(kind, psi, dpsi, rhs, n, bh, k0, nk, dev, phi=None, punctures=None, ma
     else:
         call("mgic_field_solver_vars", dpsi.handle, rhs.handle, psi.handle, n, k0, nk, _bh(bh), ptr,
              int(dev is not None))
+    if constraints:  # kind 0 only: Ham, Mom1..3 are the array's last four components
+        slab = 8 * 27 * nk * ny * nx
+        cptr = ctypes.c_void_p((dev if dev is not None else out.ctypes.data) + slab)
+        call("mgic_field_constraint_vars", psi.handle, hphi, n, k0, nk, _bh(bh),
+             *table_or_null(punctures),
+             mat.pi[0].handle if mat is not None and mat.pi is not None else None,
+             mat.potential.pot() if mat is not None else None, cptr, int(dev is not None))
     return out
 
 

@@ -23,10 +23,16 @@ Pi enter the sources as rho = Pi^2 / 2 + V (mg_ic_code_amd/matter.py); either
 flag overrides the deck's scalar_V0, scalar_mass, scalar_self_coupling and
 pi_amplitude.
 
+With --constraints the Hamiltonian and momentum constraints of the solved data
+(mg_ic_code_amd/constraints.py) are reported after the loop: one line per
+component (Ham, Mom1, Mom2, Mom3) with its max norm and its L2 norm, then
+max|Ham| / max Ham_abs.
+
 usage: python tools/run_poisson.py [params.txt] [--size N] [--boxes-per-rank x,y,z]
                                    [--max-level K] [--phi gaussian|sine]
                                    [--puncture "m x y z Px Py Pz Jx Jy Jz"]...
                                    [--potential "V0 mass lambda"] [--pi VALUE]
+                                   [--constraints]
 """
 import argparse
 import json
@@ -55,6 +61,8 @@ def main():
                     help="the scalar potential's three coefficients; overrides the deck's")
     ap.add_argument("--pi", type=float, default=None, metavar="VALUE",
                     help="a constant field velocity Pi; overrides the deck's pi_amplitude")
+    ap.add_argument("--constraints", action="store_true",
+                    help="report the constraint norms of the solved data")
     args = ap.parse_args()
     import mg_ic_code_amd as mg
     from mg_ic_code_amd.decomposition import decompose
@@ -98,11 +106,14 @@ def main():
             print(f"level {lev}: {len(g.boxes)} boxes, {cells} cells")
     t0 = time.perf_counter()
     res = poisson_solve(levels, prm, max_depth=args.max_depth, phi0=phi0, punctures=punct,
-                        matter=matter)
+                        matter=matter, constraints=args.constraints)
     mg.device_synchronize()
     dt = time.perf_counter() - t0
     for i, (nrm, it) in enumerate(zip(res.dpsi_norms, res.linear_iterations)):
         print(f"Main Loop Iteration {i + 1}: {it} BiCGStab iterations, norm of dpsi {nrm:.6e}")
+    if args.constraints:
+        for line in res.constraints.lines():
+            print(line)
     out = {"n": n, "boxes": len(boxes), "nl_iterations": len(res.dpsi_norms),
            "converged": res.converged, "seconds": round(dt, 3)}
     if punct is not None:
