@@ -637,6 +637,16 @@ MGIC_API int mgic_amr_solve(mgic_amr a, const mgic_field *phi, const mgic_field 
 MGIC_API int mgic_prof_smoother(int enable, long min_cells);
 MGIC_API int mgic_prof_smoother_read(int *launches, long *passes, double *total_ms);
 
+/* ---- the launch ledger: a host-side count of launches per compiled kernel
+ * instantiation.  Every instantiation the library can launch is listed from
+ * load time on, at zero until it runs; a two-sweep instantiation also lists
+ * the tile classes its grids contained, as "<name>#em<0|3|12|15>".  dump
+ * writes one "name<TAB>count" line per entry, sorted by name; reset zeroes
+ * the counts.  With MGIC_LAUNCH_LEDGER=PATH in the environment the library
+ * also writes PATH.<pid> when it unloads. */
+MGIC_API int mgic_launch_ledger_dump(const char *path);
+MGIC_API int mgic_launch_ledger_reset(void);
+
 #ifdef __cplusplus
 }
 #endif

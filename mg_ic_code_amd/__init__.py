@@ -23,6 +23,8 @@ from .core import (  # noqa: F401
     bicgstab_on_device,
     defineOperatorFactory,
     device_synchronize,
+    launch_ledger,
+    launch_ledger_reset,
     prof_smoother,
     prof_smoother_read,
     set_binary_bh_coefs,

@@ -246,6 +246,8 @@ SIGNATURES = {
     "mgic_host_free": [c_void_p],
     "mgic_prof_smoother": [c_int, c_long],
     "mgic_prof_smoother_read": [PI, POINTER(c_long), PD],
+    "mgic_launch_ledger_dump": [c_char_p],
+    "mgic_launch_ledger_reset": [],
     # ChomboFortran drop-ins (include/mgic_chf.h); argtypes left open
     "gsrbhelmholtzvc3d_": None,
     "vccomputeop3d_": None,

@@ -49,6 +49,8 @@ __all__ = [
     "set_nl_coefs",
     "prof_smoother",
     "prof_smoother_read",
+    "launch_ledger",
+    "launch_ledger_reset",
     "MgicError",
 ]
 
@@ -948,6 +950,38 @@ def prof_smoother(enable: bool, min_cells: int = 0, per_relax: bool = False) -> 
     or (per_relax) one pair per run of consecutive launches in a relax call
     (fewer event records in the timed stream; time / launches = the average)."""
     call("mgic_prof_smoother", (2 if per_relax else 1) if enable else 0, int(min_cells))
+
+
+def read_launch_ledger(path: str) -> dict:
+    """A ledger file (mgic_launch_ledger_dump, MGIC_LAUNCH_LEDGER) as {name: count}."""
+    out = {}
+    with open(path) as f:
+        for line in f:
+            name, _, count = line.rstrip("\n").rpartition("\t")
+            if name:
+                out[name] = int(count)
+    return out
+
+
+def launch_ledger() -> dict:
+    """{kernel instantiation: launches so far in this process}: every
+    instantiation the library can launch is a key, at 0 until it runs; a
+    two-sweep instantiation also has "<name>#em<0|3|12|15>" keys, the launches
+    whose grid contained that tile class."""
+    import os
+    import tempfile
+
+    fd, path = tempfile.mkstemp(prefix="mgic_ledger_")
+    os.close(fd)
+    try:
+        call("mgic_launch_ledger_dump", path.encode())
+        return read_launch_ledger(path)
+    finally:
+        os.unlink(path)
+
+
+def launch_ledger_reset() -> None:
+    call("mgic_launch_ledger_reset")
 
 
 def prof_smoother_read() -> Tuple[int, int, float]:

@@ -1,5 +1,8 @@
 // capi.cpp -- extern "C" boundary (include/mgic.h) over the C++ layer.
+#include <unistd.h>
+
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -7,6 +10,7 @@
 
 #include "../../include/mgic.h"
 #include "amr.hpp"
+#include "launch_ledger.hpp"
 #include "mixed.hpp"
 #include "op.hpp"
 #include "regrid.hpp"
@@ -64,6 +68,31 @@ int guard(F &&f) {
 }
 
 #define NEED(p) MGIC_CHECK((p) != nullptr, "null argument: " #p)
+
+// the launch ledger (launch_ledger.hpp) as text: one "name<TAB>count" line
+// per entry, sorted by name
+void ledger_write(const std::string &path) {
+  auto rows = ledger::snapshot();
+  std::sort(rows.begin(), rows.end());
+  FILE *f = std::fopen(path.c_str(), "w");
+  if (!f) throw Error(kBadArg, "launch ledger: cannot write " + path);
+  for (const auto &r : rows) std::fprintf(f, "%s\t%llu\n", r.first.c_str(), r.second);
+  std::fclose(f);
+}
+
+// MGIC_LAUNCH_LEDGER=PATH: the ledger goes to PATH.<pid> when the library
+// unloads (a whole test suite surveyed from its command line, children
+// included)
+struct LedgerAtUnload {
+  ~LedgerAtUnload() {
+    const char *p = std::getenv("MGIC_LAUNCH_LEDGER");
+    if (!p || !*p) return;
+    try {
+      ledger_write(std::string(p) + "." + std::to_string((long)getpid()));
+    } catch (...) {
+    }
+  }
+} g_ledger_at_unload;
 
 OpParams to_op(const mgic_op_params *p) {
   OpParams o;
@@ -1917,6 +1946,16 @@ MGIC_API int mgic_prof_smoother_read(int *launches, long *passes, double *total_
     if (passes) *passes = np;
     if (total_ms) *total_ms = t;
   });
+}
+
+MGIC_API int mgic_launch_ledger_dump(const char *path) {
+  return guard([&] {
+    NEED(path);
+    ledger_write(path);
+  });
+}
+MGIC_API int mgic_launch_ledger_reset(void) {
+  return guard([&] { ledger::reset(); });
 }
 
 }  // extern "C"

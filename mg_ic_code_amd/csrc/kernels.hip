@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "kernels.hpp"
+#include "launch_ledger.hpp"
 
 namespace mgic {
 namespace kern {
@@ -2062,11 +2063,13 @@ void gsrb_pass(double *u, const double *rhs, const double *a, const double *b, c
   const dim3 grid((unsigned)((npairs + TX - 1) / TX), (unsigned)((g.ny + TY - 1) / TY),
                   (unsigned)g.nz);
   if (lam) {
-    if (s.bconst) k_gsrb<true, true><<<grid, kBlock, 0, st>>>(u, rhs, a, b, lam, g, s, colour);
-    else k_gsrb<true, false><<<grid, kBlock, 0, st>>>(u, rhs, a, b, lam, g, s, colour);
+    // (a stored lambda comes from the ChomboFortran drop-in alone, whose
+    // coefficients never claim a constant bCoef: the bCoef field is read)
+    MGIC_CHECK(!s.bconst, "colour pass with a stored lambda: constant bCoef");
+    ledger::launch<k_gsrb<true, false>>(grid, kBlock, 0, st, u, rhs, a, b, lam, g, s, colour);
   } else {
-    if (s.bconst) k_gsrb<false, true><<<grid, kBlock, 0, st>>>(u, rhs, a, b, nullptr, g, s, colour);
-    else k_gsrb<false, false><<<grid, kBlock, 0, st>>>(u, rhs, a, b, nullptr, g, s, colour);
+    if (s.bconst) ledger::launch<k_gsrb<false, true>>(grid, kBlock, 0, st, u, rhs, a, b, nullptr, g, s, colour);
+    else ledger::launch<k_gsrb<false, false>>(grid, kBlock, 0, st, u, rhs, a, b, nullptr, g, s, colour);
   }
   check_launch();
 }
@@ -2074,8 +2077,8 @@ void gsrb_pass(double *u, const double *rhs, const double *a, const double *b, c
 void apply_op(double *lu, const double *u, const double *a, const double *b, const BoxArgs &g,
               const StencilCoefs &s, hipStream_t st) {
   if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
-  if (s.bconst) k_apply_op<true><<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(lu, u, a, b, g, s);
-  else k_apply_op<false><<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(lu, u, a, b, g, s);
+  if (s.bconst) ledger::launch<k_apply_op<true>>(grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st, lu, u, a, b, g, s);
+  else ledger::launch<k_apply_op<false>>(grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st, lu, u, a, b, g, s);
   check_launch();
 }
 
@@ -2098,8 +2101,8 @@ static void launch_residual(RT *r, const double *u, const double *rhs, const dou
   const dim3 t = grid_cells((g.nx + 1) / 2, g.ny, g.nz);
   const uint4 lg{t.x, t.y, (unsigned)((g.nz + kc - 1) / kc), (unsigned)kResidualBand};
   const dim3 grid(lg.x * lg.y * lg.z);
-  if (s.bconst) k_residual_zl<true, RT, NRM><<<grid, kBlock, 0, st>>>(r, u, rhs, a, b, g, s, kc, partials, lg);
-  else k_residual_zl<false, RT, NRM><<<grid, kBlock, 0, st>>>(r, u, rhs, a, b, g, s, kc, partials, lg);
+  if (s.bconst) ledger::launch<k_residual_zl<true, RT, NRM>>(grid, kBlock, 0, st, r, u, rhs, a, b, g, s, kc, partials, lg);
+  else ledger::launch<k_residual_zl<false, RT, NRM>>(grid, kBlock, 0, st, r, u, rhs, a, b, g, s, kc, partials, lg);
   check_launch();
 }
 
@@ -2137,11 +2140,11 @@ void restrict_residual(double *rc, const BoxArgs &cg, const double *u, const dou
   const int kc = 4 < cg.nz ? 4 : cg.nz;
   const int nb = ntx * nty * ((cg.nz + kc - 1) / kc);
   if (s.bconst)
-    k_restrict_zl<double, true, true><<<nb, 256, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, accu, kc, ntx,
-                                                          nty, kRestrictBand);
+    ledger::launch<k_restrict_zl<double, true, true>>(nb, 256, 0, st, rc, cg, u, rhs, a, b, fg, s,
+                                                      accu, kc, ntx, nty, kRestrictBand);
   else
-    k_restrict_zl<double, false, false><<<nb, 256, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, accu, kc, ntx,
-                                                            nty, kRestrictBand);
+    ledger::launch<k_restrict_zl<double, false, false>>(nb, 256, 0, st, rc, cg, u, rhs, a, b, fg, s,
+                                                        accu, kc, ntx, nty, kRestrictBand);
   check_launch();
 }
 
@@ -2156,23 +2159,23 @@ void prolong(double *uf, const BoxArgs &fg, const double *ec, const BoxArgs &cg,
   MGIC_CHECK(fg.nx == 2 * cg.nx && fg.ny == 2 * cg.ny && fg.nz == 2 * cg.nz,
              "prolong: fine box must be the coarse box refined by 2");
   if (type == 1)
-    k_prolong<double, 1><<<grid_cells(cg.nx, cg.ny, cg.nz), kBlock, 0, st>>>(uf, fg, ec, cg, pa);
+    ledger::launch<k_prolong<double, 1>>(grid_cells(cg.nx, cg.ny, cg.nz), kBlock, 0, st, uf, fg, ec, cg, pa);
   else
-    k_prolong<double, 0><<<grid_cells(cg.nx, cg.ny, cg.nz), kBlock, 0, st>>>(uf, fg, ec, cg, pa);
+    ledger::launch<k_prolong<double, 0>>(grid_cells(cg.nx, cg.ny, cg.nz), kBlock, 0, st, uf, fg, ec, cg, pa);
   check_launch();
 }
 
 void lambda(double *lam, const double *a, const BoxArgs &g, const StencilCoefs &s,
             hipStream_t st) {
   if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
-  k_lambda<<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(lam, a, g, s);
+  ledger::launch<k_lambda>(grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st, lam, a, g, s);
   check_launch();
 }
 
 void average(double *c, const BoxArgs &cg, const double *f, const BoxArgs &fg, int ratio,
              int harmonic, hipStream_t st) {
   if (cg.nx <= 0 || cg.ny <= 0 || cg.nz <= 0) return;
-  k_average<<<grid_cells(cg.nx, cg.ny, cg.nz), kBlock, 0, st>>>(c, cg, f, fg, ratio, harmonic);
+  ledger::launch<k_average>(grid_cells(cg.nx, cg.ny, cg.nz), kBlock, 0, st, c, cg, f, fg, ratio, harmonic);
   check_launch();
 }
 
@@ -2183,7 +2186,7 @@ void fill_bc(double *u, const BoxArgs &g, hipStream_t st) {
     const int dir = face >> 1;
     const int d1 = dir == 0 ? 1 : 0, d2 = dir == 2 ? 1 : 2;
     const dim3 grid((unsigned)((n[d1] + 255) / 256), (unsigned)n[d2], 1);
-    k_fill_bc_face<<<grid, dim3(256, 1, 1), 0, st>>>(u, g, face);
+    ledger::launch<k_fill_bc_face>(grid, dim3(256, 1, 1), 0, st, u, g, face);
     check_launch();
   }
 }
@@ -2200,13 +2203,13 @@ void blas(int kind, double *x, const double *y, const double *z, double s, doubl
   if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
   const dim3 grid = grid_cells(g.nx, g.ny, g.nz);
   switch (kind) {
-    case 0: k_blas<0><<<grid, kBlock, 0, st>>>(x, y, z, s, t, g); break;
-    case 1: k_blas<1><<<grid, kBlock, 0, st>>>(x, y, z, s, t, g); break;
-    case 2: k_blas<2><<<grid, kBlock, 0, st>>>(x, y, z, s, t, g); break;
-    case 3: k_blas<3><<<grid, kBlock, 0, st>>>(x, y, z, s, t, g); break;
-    case 4: k_blas<4><<<grid, kBlock, 0, st>>>(x, y, z, s, t, g); break;
-    case 5: k_blas<5><<<grid, kBlock, 0, st>>>(x, y, z, s, t, g); break;
-    case 6: k_blas<6><<<grid, kBlock, 0, st>>>(x, y, z, s, t, g); break;
+    case 0: ledger::launch<k_blas<0>>(grid, kBlock, 0, st, x, y, z, s, t, g); break;
+    case 1: ledger::launch<k_blas<1>>(grid, kBlock, 0, st, x, y, z, s, t, g); break;
+    case 2: ledger::launch<k_blas<2>>(grid, kBlock, 0, st, x, y, z, s, t, g); break;
+    case 3: ledger::launch<k_blas<3>>(grid, kBlock, 0, st, x, y, z, s, t, g); break;
+    case 4: ledger::launch<k_blas<4>>(grid, kBlock, 0, st, x, y, z, s, t, g); break;
+    case 5: ledger::launch<k_blas<5>>(grid, kBlock, 0, st, x, y, z, s, t, g); break;
+    case 6: ledger::launch<k_blas<6>>(grid, kBlock, 0, st, x, y, z, s, t, g); break;
     default: throw Error(kBadArg, "blas: bad kind");
   }
   check_launch();
@@ -2219,12 +2222,12 @@ int reduce_partial(int kind, const double *x, const double *y, const BoxArgs &g,
   const long nb = reduce_blocks(g);
   const dim3 grid((unsigned)nb), block(RB);
   switch (kind) {
-    case 0: k_reduce_partial<0><<<grid, block, 0, st>>>(x, y, g, partials); break;
-    case 1: k_reduce_partial<1><<<grid, block, 0, st>>>(x, y, g, partials); break;
-    case 2: k_reduce_partial<2><<<grid, block, 0, st>>>(x, y, g, partials); break;
-    case 3: k_reduce_partial<3><<<grid, block, 0, st>>>(x, y, g, partials); break;
-    case 4: k_reduce_partial<4><<<grid, block, 0, st>>>(x, y, g, partials); break;
-    case 5: k_reduce_partial<5><<<grid, block, 0, st>>>(x, y, g, partials); break;
+    case 0: ledger::launch<k_reduce_partial<0>>(grid, block, 0, st, x, y, g, partials); break;
+    case 1: ledger::launch<k_reduce_partial<1>>(grid, block, 0, st, x, y, g, partials); break;
+    case 2: ledger::launch<k_reduce_partial<2>>(grid, block, 0, st, x, y, g, partials); break;
+    case 3: ledger::launch<k_reduce_partial<3>>(grid, block, 0, st, x, y, g, partials); break;
+    case 4: ledger::launch<k_reduce_partial<4>>(grid, block, 0, st, x, y, g, partials); break;
+    case 5: ledger::launch<k_reduce_partial<5>>(grid, block, 0, st, x, y, g, partials); break;
     default: throw Error(kBadArg, "reduce: bad kind");
   }
   check_launch();
@@ -2234,12 +2237,12 @@ int reduce_partial(int kind, const double *x, const double *y, const BoxArgs &g,
 void reduce_final(int kind, const double *partials, int n, double *out, hipStream_t st,
                   const HostPub &pub) {
   switch (kind) {
-    case 0: k_reduce_final<0><<<1, RB, 0, st>>>(partials, n, out, pub); break;
-    case 1: k_reduce_final<1><<<1, RB, 0, st>>>(partials, n, out, pub); break;
-    case 2: k_reduce_final<2><<<1, RB, 0, st>>>(partials, n, out, pub); break;
-    case 3: k_reduce_final_wide<3><<<1, 1024, 0, st>>>(partials, n, out, pub); break;
-    case 4: k_reduce_final_wide<4><<<1, 1024, 0, st>>>(partials, n, out, pub); break;
-    case 5: k_reduce_final_wide<5><<<1, 1024, 0, st>>>(partials, n, out, pub); break;
+    case 0: ledger::launch<k_reduce_final<0>>(1, RB, 0, st, partials, n, out, pub); break;
+    case 1: ledger::launch<k_reduce_final<1>>(1, RB, 0, st, partials, n, out, pub); break;
+    case 2: ledger::launch<k_reduce_final<2>>(1, RB, 0, st, partials, n, out, pub); break;
+    case 3: ledger::launch<k_reduce_final_wide<3>>(1, 1024, 0, st, partials, n, out, pub); break;
+    case 4: ledger::launch<k_reduce_final_wide<4>>(1, 1024, 0, st, partials, n, out, pub); break;
+    case 5: ledger::launch<k_reduce_final_wide<5>>(1, 1024, 0, st, partials, n, out, pub); break;
     default: throw Error(kBadArg, "reduce: bad kind");
   }
   check_launch();
@@ -2247,7 +2250,7 @@ void reduce_final(int kind, const double *partials, int n, double *out, hipStrea
 
 void publish_result(const double *d_val, const HostPub &pub, hipStream_t st) {
   if (!pub.val) return;
-  k_publish<<<1, 64, 0, st>>>(d_val, pub);
+  ledger::launch<k_publish>(1, 64, 0, st, d_val, pub);
   check_launch();
 }
 
@@ -2258,9 +2261,9 @@ int axpy2_reduce(int kind, double *s, const double *r, const double *v, double c
   const long nb = reduce_blocks(g);
   const dim3 grid((unsigned)nb), block(RB);
   switch (kind) {
-    case 1: k_axpy2_reduce<1><<<grid, block, 0, st>>>(s, r, v, ca, e, pt, cb, g, partials); break;
-    case 2: k_axpy2_reduce<2><<<grid, block, 0, st>>>(s, r, v, ca, e, pt, cb, g, partials); break;
-    case 3: k_axpy2_reduce<3><<<grid, block, 0, st>>>(s, r, v, ca, e, pt, cb, g, partials); break;
+    case 1: ledger::launch<k_axpy2_reduce<1>>(grid, block, 0, st, s, r, v, ca, e, pt, cb, g, partials); break;
+    case 2: ledger::launch<k_axpy2_reduce<2>>(grid, block, 0, st, s, r, v, ca, e, pt, cb, g, partials); break;
+    case 3: ledger::launch<k_axpy2_reduce<3>>(grid, block, 0, st, s, r, v, ca, e, pt, cb, g, partials); break;
     default: throw Error(kBadArg, "axpy2_reduce: bad kind");
   }
   check_launch();
@@ -2271,7 +2274,7 @@ int dot2_partial(const double *t, const double *s, const BoxArgs &g, double *pts
                  hipStream_t st) {
   if ((long)g.nx * g.ny * g.nz <= 0) return 0;
   const long nb = reduce_blocks(g);
-  k_dot2<<<dim3((unsigned)nb), dim3(RB), 0, st>>>(t, s, g, pts, ptt);
+  ledger::launch<k_dot2>(dim3((unsigned)nb), dim3(RB), 0, st, t, s, g, pts, ptt);
   check_launch();
   return (int)nb;
 }
@@ -2279,7 +2282,7 @@ int dot2_partial(const double *t, const double *s, const BoxArgs &g, double *pts
 void bicg_p(double *p, const double *v, const double *r, double beta, double c, const BoxArgs &g,
             hipStream_t st) {
   if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
-  k_bicg_p<<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(p, v, r, beta, c, g);
+  ledger::launch<k_bicg_p>(grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st, p, v, r, beta, c, g);
   check_launch();
 }
 
@@ -2294,8 +2297,8 @@ void copy_items(const CopyItem *d_items, int nitems, long max_cells, double *con
   const long per = 256L * kCopyEpt;
   long bx = (max_cells + per - 1) / per;
   if (bx > 1024) bx = 1024;
-  k_copy_items<double><<<dim3((unsigned)bx, (unsigned)nitems), dim3(256), 0, st>>>(
-      d_items, src_tab, src_buf, dst_tab, dst_buf);
+  ledger::launch<k_copy_items<double>>(dim3((unsigned)bx, (unsigned)nitems), dim3(256), 0, st,
+                                       d_items, src_tab, src_buf, dst_tab, dst_buf);
   check_launch();
 }
 
@@ -2345,17 +2348,17 @@ static void launch_binary_bh(double *acoef, double *rhs, const double *psi, cons
   const dim3 grid = grid_cells(g.nx, g.ny, g.nz);
   const PunctureArg<false> none;
   if (t && phi)
-    k_binary_bh<INTEGRAND, true, true, MATTER><<<grid, kBlock, 0, st>>>(acoef, rhs, psi, phi, g,
-                                                                        dx, p, table_arg(t), m);
+    ledger::launch<k_binary_bh<INTEGRAND, true, true, MATTER>>(grid, kBlock, 0, st, acoef, rhs, psi,
+                                                               phi, g, dx, p, table_arg(t), m);
   else if (t)
-    k_binary_bh<INTEGRAND, false, true, MATTER><<<grid, kBlock, 0, st>>>(
-        acoef, rhs, psi, nullptr, g, dx, p, table_arg(t), m);
+    ledger::launch<k_binary_bh<INTEGRAND, false, true, MATTER>>(
+        grid, kBlock, 0, st, acoef, rhs, psi, nullptr, g, dx, p, table_arg(t), m);
   else if (phi)
-    k_binary_bh<INTEGRAND, true, false, MATTER><<<grid, kBlock, 0, st>>>(acoef, rhs, psi, phi, g,
-                                                                         dx, p, none, m);
+    ledger::launch<k_binary_bh<INTEGRAND, true, false, MATTER>>(grid, kBlock, 0, st, acoef, rhs, psi,
+                                                                phi, g, dx, p, none, m);
   else
-    k_binary_bh<INTEGRAND, false, false, MATTER><<<grid, kBlock, 0, st>>>(acoef, rhs, psi, nullptr,
-                                                                          g, dx, p, none, m);
+    ledger::launch<k_binary_bh<INTEGRAND, false, false, MATTER>>(grid, kBlock, 0, st, acoef, rhs,
+                                                                 psi, nullptr, g, dx, p, none, m);
   check_launch();
 }
 template <bool INTEGRAND>
@@ -2391,17 +2394,17 @@ static void launch_regrid_condition(double *out, const double *psi, const double
   const dim3 grid = grid_cells(g.nx, g.ny, g.nz);
   const PunctureArg<false> none;
   if (table && phi)
-    k_regrid_condition<true, true, MATTER><<<grid, kBlock, 0, st>>>(out, psi, phi, g, dx, p,
-                                                                    table_arg(table), m);
+    ledger::launch<k_regrid_condition<true, true, MATTER>>(grid, kBlock, 0, st, out, psi, phi, g, dx,
+                                                           p, table_arg(table), m);
   else if (table)
-    k_regrid_condition<false, true, MATTER><<<grid, kBlock, 0, st>>>(out, psi, nullptr, g, dx, p,
-                                                                     table_arg(table), m);
+    ledger::launch<k_regrid_condition<false, true, MATTER>>(grid, kBlock, 0, st, out, psi, nullptr,
+                                                            g, dx, p, table_arg(table), m);
   else if (phi)
-    k_regrid_condition<true, false, MATTER><<<grid, kBlock, 0, st>>>(out, psi, phi, g, dx, p, none,
-                                                                     m);
+    ledger::launch<k_regrid_condition<true, false, MATTER>>(grid, kBlock, 0, st, out, psi, phi, g,
+                                                            dx, p, none, m);
   else
-    k_regrid_condition<false, false, MATTER><<<grid, kBlock, 0, st>>>(out, psi, nullptr, g, dx, p,
-                                                                      none, m);
+    ledger::launch<k_regrid_condition<false, false, MATTER>>(grid, kBlock, 0, st, out, psi, nullptr,
+                                                             g, dx, p, none, m);
   check_launch();
 }
 
@@ -2430,19 +2433,19 @@ void tag_lattice(unsigned char *mask, const double *cond, const BoxArgs &g, doub
   }
   t.grow = grow;
   t.c = c;
-  k_tag_lattice<<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(mask, cond, g, tag_val, t);
+  ledger::launch<k_tag_lattice>(grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st, mask, cond, g, tag_val, t);
   check_launch();
 }
 
 void lap_psi(double *l, const double *psi, const BoxArgs &g, double dx, hipStream_t st) {
   if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
-  k_lap_psi<<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(l, psi, g, dx);
+  ledger::launch<k_lap_psi>(grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st, l, psi, g, dx);
   check_launch();
 }
 
 void rho_grad_phi(double *r, const double *phi, const BoxArgs &g, double dx, hipStream_t st) {
   if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
-  k_rho_grad_phi<<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(r, phi, g, dx);
+  ledger::launch<k_rho_grad_phi>(grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st, r, phi, g, dx);
   check_launch();
 }
 
@@ -2454,17 +2457,17 @@ static void launch_output_vars(double *out, const double *psi, const double *dps
   const dim3 grid = grid_cells(g.nx, g.ny, nk);
   const PunctureArg<false> none;
   if (t && phi)
-    k_output_vars<KIND, true, true, MATTER><<<grid, kBlock, 0, st>>>(
-        out, psi, dpsi, rhs, phi, g, k0, nk, dx, p, table_arg(t), m);
+    ledger::launch<k_output_vars<KIND, true, true, MATTER>>(
+        grid, kBlock, 0, st, out, psi, dpsi, rhs, phi, g, k0, nk, dx, p, table_arg(t), m);
   else if (t)
-    k_output_vars<KIND, false, true, MATTER><<<grid, kBlock, 0, st>>>(
-        out, psi, dpsi, rhs, nullptr, g, k0, nk, dx, p, table_arg(t), m);
+    ledger::launch<k_output_vars<KIND, false, true, MATTER>>(
+        grid, kBlock, 0, st, out, psi, dpsi, rhs, nullptr, g, k0, nk, dx, p, table_arg(t), m);
   else if (phi)
-    k_output_vars<KIND, true, false, MATTER><<<grid, kBlock, 0, st>>>(out, psi, dpsi, rhs, phi, g,
-                                                                      k0, nk, dx, p, none, m);
+    ledger::launch<k_output_vars<KIND, true, false, MATTER>>(
+        grid, kBlock, 0, st, out, psi, dpsi, rhs, phi, g, k0, nk, dx, p, none, m);
   else
-    k_output_vars<KIND, false, false, MATTER><<<grid, kBlock, 0, st>>>(
-        out, psi, dpsi, rhs, nullptr, g, k0, nk, dx, p, none, m);
+    ledger::launch<k_output_vars<KIND, false, false, MATTER>>(
+        grid, kBlock, 0, st, out, psi, dpsi, rhs, nullptr, g, k0, nk, dx, p, none, m);
 }
 
 void output_vars(int kind, double *out, const double *psi, const double *dpsi, const double *rhs,
@@ -2492,17 +2495,17 @@ static void launch_constraints(const ConstraintOut &o, const double *psi, const 
   const dim3 grid = grid_cells(g.nx, g.ny, nk);
   const PunctureArg<false> none;
   if (t && phi)
-    k_constraints<true, true, MATTER><<<grid, kBlock, 0, st>>>(o, psi, phi, g, k0, dx, p,
-                                                               table_arg(t), m);
+    ledger::launch<k_constraints<true, true, MATTER>>(grid, kBlock, 0, st, o, psi, phi, g, k0, dx, p,
+                                                      table_arg(t), m);
   else if (t)
-    k_constraints<false, true, MATTER><<<grid, kBlock, 0, st>>>(o, psi, nullptr, g, k0, dx, p,
-                                                                table_arg(t), m);
+    ledger::launch<k_constraints<false, true, MATTER>>(grid, kBlock, 0, st, o, psi, nullptr, g, k0,
+                                                       dx, p, table_arg(t), m);
   else if (phi)
-    k_constraints<true, false, MATTER><<<grid, kBlock, 0, st>>>(o, psi, phi, g, k0, dx, p, none,
-                                                                m);
+    ledger::launch<k_constraints<true, false, MATTER>>(grid, kBlock, 0, st, o, psi, phi, g, k0, dx,
+                                                       p, none, m);
   else
-    k_constraints<false, false, MATTER><<<grid, kBlock, 0, st>>>(o, psi, nullptr, g, k0, dx, p,
-                                                                 none, m);
+    ledger::launch<k_constraints<false, false, MATTER>>(grid, kBlock, 0, st, o, psi, nullptr, g, k0,
+                                                        dx, p, none, m);
   check_launch();
 }
 
@@ -2529,9 +2532,9 @@ void fill_phi(int profile, double *phi, const BoxArgs &g, double dx, const BhPar
   if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
   const dim3 grid = grid_cells(g.nx + 2, g.ny + 2, g.nz + 2);
   if (profile == kPhiGaussian)
-    k_fill_phi<kPhiGaussian><<<grid, kBlock, 0, st>>>(phi, g, dx, p);
+    ledger::launch<k_fill_phi<kPhiGaussian>>(grid, kBlock, 0, st, phi, g, dx, p);
   else
-    k_fill_phi<kPhiSine><<<grid, kBlock, 0, st>>>(phi, g, dx, p);
+    ledger::launch<k_fill_phi<kPhiSine>>(grid, kBlock, 0, st, phi, g, dx, p);
   check_launch();
 }
 
@@ -2551,8 +2554,8 @@ __global__ __launch_bounds__(256) void k_incr_grown(double *__restrict__ x,
 
 void incr_grown(double *x, const double *y, const BoxArgs &g, int grow, hipStream_t st) {
   if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
-  k_incr_grown<<<grid_cells(g.nx + 2 * grow, g.ny + 2 * grow, g.nz + 2 * grow), kBlock, 0, st>>>(
-      x, y, g, grow);
+  ledger::launch<k_incr_grown>(grid_cells(g.nx + 2 * grow, g.ny + 2 * grow, g.nz + 2 * grow), kBlock,
+                               0, st, x, y, g, grow);
   check_launch();
 }
 
@@ -2578,11 +2581,11 @@ void restrict_residual_f(float *rc, const BoxArgs &cg, const float *u, const flo
   const int kc = 2 < cg.nz ? 2 : cg.nz;
   const int nb = ntx * nty * ((cg.nz + kc - 1) / kc);
   if (s.bconst)
-    k_restrict_zl<float, true, false><<<nb, 256, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, 0, kc, ntx, nty,
-                                                          kRestrictBandF);
+    ledger::launch<k_restrict_zl<float, true, false>>(nb, 256, 0, st, rc, cg, u, rhs, a, b, fg, s, 0,
+                                                      kc, ntx, nty, kRestrictBandF);
   else
-    k_restrict_zl<float, false, false><<<nb, 256, 0, st>>>(rc, cg, u, rhs, a, b, fg, s, 0, kc, ntx, nty,
-                                                           kRestrictBandF);
+    ledger::launch<k_restrict_zl<float, false, false>>(nb, 256, 0, st, rc, cg, u, rhs, a, b, fg, s, 0,
+                                                       kc, ntx, nty, kRestrictBandF);
   check_launch();
 }
 
@@ -2597,9 +2600,9 @@ void prolong_f(float *uf, const BoxArgs &fg, const float *ec, const BoxArgs &cg,
   MGIC_CHECK(fg.nx == 2 * cg.nx && fg.ny == 2 * cg.ny && fg.nz == 2 * cg.nz,
              "prolong: fine box must be the coarse box refined by 2");
   if (type == 1)
-    k_prolong<float, 1><<<grid_cells(cg.nx, cg.ny, cg.nz), kBlock, 0, st>>>(uf, fg, ec, cg, pa);
+    ledger::launch<k_prolong<float, 1>>(grid_cells(cg.nx, cg.ny, cg.nz), kBlock, 0, st, uf, fg, ec, cg, pa);
   else
-    k_prolong<float, 0><<<grid_cells(cg.nx, cg.ny, cg.nz), kBlock, 0, st>>>(uf, fg, ec, cg, pa);
+    ledger::launch<k_prolong<float, 0>>(grid_cells(cg.nx, cg.ny, cg.nz), kBlock, 0, st, uf, fg, ec, cg, pa);
   check_launch();
 }
 
@@ -2609,15 +2612,15 @@ void copy_items_f(const CopyItem *d_items, int nitems, long max_cells, float *co
   const long per = 256L * kCopyEpt;
   long bx = (max_cells + per - 1) / per;
   if (bx > 1024) bx = 1024;
-  k_copy_items<float><<<dim3((unsigned)bx, (unsigned)nitems), dim3(256), 0, st>>>(
-      d_items, src_tab, src_buf, dst_tab, dst_buf);
+  ledger::launch<k_copy_items<float>>(dim3((unsigned)bx, (unsigned)nitems), dim3(256), 0, st,
+                                      d_items, src_tab, src_buf, dst_tab, dst_buf);
   check_launch();
 }
 
 void to_float(float *d, const double *s, const BoxArgs &g, int grow, hipStream_t st) {
   if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
-  k_to_float<<<grid_cells(g.nx + 2 * grow, g.ny + 2 * grow, g.nz + 2 * grow), kBlock, 0, st>>>(
-      d, s, g, grow);
+  ledger::launch<k_to_float>(grid_cells(g.nx + 2 * grow, g.ny + 2 * grow, g.nz + 2 * grow), kBlock, 0,
+                             st, d, s, g, grow);
   check_launch();
 }
 
@@ -2628,20 +2631,20 @@ void cf_interp(double *u, const double *coarse_stage, const BoxArgs &g, const CF
   const int d0 = dir == 0 ? 1 : 0, d1 = dir == 2 ? 1 : 2;
   if (n[dir] < 2) throw Error(kBadArg, "cf_interp: a box needs 2 cells normal to a CF face");
   const dim3 grid((unsigned)((n[d0] + 255) / 256), (unsigned)n[d1]);
-  if (homogeneous) k_cf_interp<true><<<grid, 256, 0, st>>>(u, coarse_stage, g, c);
-  else k_cf_interp<false><<<grid, 256, 0, st>>>(u, coarse_stage, g, c);
+  if (homogeneous) ledger::launch<k_cf_interp<true>>(grid, 256, 0, st, u, coarse_stage, g, c);
+  else ledger::launch<k_cf_interp<false>>(grid, 256, 0, st, u, coarse_stage, g, c);
   check_launch();
 }
 
 void incr_f(double *x, const float *y, const BoxArgs &g, hipStream_t st) {
   if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
-  k_incr_f<<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(x, y, g);
+  ledger::launch<k_incr_f>(grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st, x, y, g);
   check_launch();
 }
 
 void copy_f(float *d, const float *s, const BoxArgs &g, hipStream_t st) {
   if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return;
-  k_copy_f<<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st>>>(d, s, g);
+  ledger::launch<k_copy_f>(grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st, d, s, g);
   check_launch();
 }
 
@@ -2652,7 +2655,7 @@ int bicg_dev_parts(const BoxArgs &g) { return (int)reduce_blocks(g); }
 
 void bicg_dev_p(BicgState *st, double *p, double *w, const double *v, const double *r,
                 const double *lam, const BoxArgs &g, hipStream_t st_) {
-  k_bicgd_p<<<grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st_>>>(st, p, w, v, r, lam, g);
+  ledger::launch<k_bicgd_p>(grid_cells(g.nx, g.ny, g.nz), kBlock, 0, st_, st, p, w, v, r, lam, g);
   check_launch();
 }
 
@@ -2661,8 +2664,10 @@ void bicg_dev_apply_dot(BicgState *st, double *v, const double *pt, const double
                         double *parts, unsigned int *cnt, hipStream_t st_) {
   const dim3 grid((unsigned)reduce_blocks(g)), block(RB);
   cnt += 0 * kBicgCntWords;
-  if (s.bconst) k_bicgd_apply_dot<true><<<grid, block, 0, st_>>>(st, v, pt, rt, a, b, g, s, parts, cnt);
-  else k_bicgd_apply_dot<false><<<grid, block, 0, st_>>>(st, v, pt, rt, a, b, g, s, parts, cnt);
+  // (constant bCoef only: the device loop runs where preCond is one two-sweep
+  // launch, BiCGStabSolver::deviceApplies, and that kernel takes no bCoef field)
+  MGIC_CHECK(s.bconst, "device BiCGStab: variable bCoef");
+  ledger::launch<k_bicgd_apply_dot<true>>(grid, block, 0, st_, st, v, pt, rt, a, b, g, s, parts, cnt);
   check_launch();
 }
 
@@ -2672,9 +2677,9 @@ void bicg_dev_s(BicgState *st, double *s, double *w, const double *r, const doub
   const dim3 grid((unsigned)reduce_blocks(g)), block(RB);
   cnt += 1 * kBicgCntWords;
   switch (norm_kind) {
-    case 1: k_bicgd_s<1><<<grid, block, 0, st_>>>(st, s, w, r, v, lam, g, parts, cnt); break;
-    case 2: k_bicgd_s<2><<<grid, block, 0, st_>>>(st, s, w, r, v, lam, g, parts, cnt); break;
-    case 3: k_bicgd_s<3><<<grid, block, 0, st_>>>(st, s, w, r, v, lam, g, parts, cnt); break;
+    case 1: ledger::launch<k_bicgd_s<1>>(grid, block, 0, st_, st, s, w, r, v, lam, g, parts, cnt); break;
+    case 2: ledger::launch<k_bicgd_s<2>>(grid, block, 0, st_, st, s, w, r, v, lam, g, parts, cnt); break;
+    case 3: ledger::launch<k_bicgd_s<3>>(grid, block, 0, st_, st, s, w, r, v, lam, g, parts, cnt); break;
     default: throw Error(kBadArg, "bicg_dev_s: bad norm kind");
   }
   check_launch();
@@ -2685,12 +2690,9 @@ void bicg_dev_apply_dot2(BicgState *st, const double *stv, const double *s, cons
                          double *parts_ts, double *parts_tt, unsigned int *cnt, hipStream_t st_) {
   const dim3 grid((unsigned)reduce_blocks(g)), block(RB);
   cnt += 2 * kBicgCntWords;
-  if (sc.bconst)
-    k_bicgd_apply_dot2<true><<<grid, block, 0, st_>>>(st, stv, s, a, b, g, sc, parts_ts, parts_tt,
-                                                      cnt);
-  else
-    k_bicgd_apply_dot2<false><<<grid, block, 0, st_>>>(st, stv, s, a, b, g, sc, parts_ts, parts_tt,
-                                                       cnt);
+  MGIC_CHECK(sc.bconst, "device BiCGStab: variable bCoef");
+  ledger::launch<k_bicgd_apply_dot2<true>>(grid, block, 0, st_, st, stv, s, a, b, g, sc, parts_ts,
+                                           parts_tt, cnt);
   check_launch();
 }
 
@@ -2700,16 +2702,14 @@ void bicg_dev_r(BicgState *st, double *r, double *e, const double *s, const doub
                 double *parts_d, unsigned int *cnt, hipStream_t st_) {
   const dim3 grid((unsigned)reduce_blocks(g)), block(RB);
   cnt += 3 * kBicgCntWords;
-#define MGIC_BICG_R(K, BC)                                                                   \
-  k_bicgd_r<K, BC><<<grid, block, 0, st_>>>(st, r, e, s, a, b, sc, pt, stv, rt, g, parts_n,  \
-                                            parts_d, cnt)
-  switch (norm_kind * 2 + (sc.bconst ? 1 : 0)) {
-    case 2: MGIC_BICG_R(1, false); break;
-    case 3: MGIC_BICG_R(1, true); break;
-    case 4: MGIC_BICG_R(2, false); break;
-    case 5: MGIC_BICG_R(2, true); break;
-    case 6: MGIC_BICG_R(3, false); break;
-    case 7: MGIC_BICG_R(3, true); break;
+  MGIC_CHECK(sc.bconst, "device BiCGStab: variable bCoef");
+#define MGIC_BICG_R(K)                                                                          \
+  ledger::launch<k_bicgd_r<K, true>>(grid, block, 0, st_, st, r, e, s, a, b, sc, pt, stv, rt, g, \
+                                     parts_n, parts_d, cnt)
+  switch (norm_kind) {
+    case 1: MGIC_BICG_R(1); break;
+    case 2: MGIC_BICG_R(2); break;
+    case 3: MGIC_BICG_R(3); break;
     default: throw Error(kBadArg, "bicg_dev_r: bad norm kind");
   }
 #undef MGIC_BICG_R
@@ -2718,7 +2718,7 @@ void bicg_dev_r(BicgState *st, double *r, double *e, const double *s, const doub
 
 void bicg_dev_publish(const BicgState *st, BicgState *host, unsigned long long *seq,
                       unsigned long long seqv, hipStream_t st_) {
-  k_bicgd_publish<<<1, 64, 0, st_>>>(st, host, seq, seqv);
+  ledger::launch<k_bicgd_publish>(1, 64, 0, st_, st, host, seq, seqv);
   check_launch();
 }
 

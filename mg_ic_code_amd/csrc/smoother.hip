@@ -38,6 +38,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "launch_ledger.hpp"
 #include "sweep_util.hpp"
 
 namespace mgic {
@@ -1018,8 +1019,8 @@ static void launch_fused6(T *u_out, T *u_in, const T *rhs, const T *a, const T *
   const int nblocks = ntx * nty * ntz;
   const dim3 grid((unsigned)nblocks), block(NT);
 #define MGIC_F6(Z, B, A)                                                                     \
-  k_gsrb_fused6<T, TX, TY, NT, Z, B, A><<<grid, block, 0, st>>>(u_out, acc, u_in, rhs, a, b, g, \
-                                                                s, kc, ntx, nty, nblocks)
+  ledger::launch<k_gsrb_fused6<T, TX, TY, NT, Z, B, A>>(grid, block, 0, st, u_out, acc, u_in, rhs, \
+                                                        a, b, g, s, kc, ntx, nty, nblocks)
   if (acc) {  // last sweep of a V-cycle at depth 0: phi += e in the same pass
     if (zero_in) throw Error(kBadArg, "fused sweep: accumulate on a zero input");
     if (s.bconst) MGIC_F6(false, true, true);
@@ -1036,23 +1037,20 @@ static void launch_fused6(T *u_out, T *u_in, const T *rhs, const T *a, const T *
   if (e != hipSuccess) throw Error(kHipErr, std::string("fused sweep launch: ") + hipGetErrorString(e));
 }
 
-// the sweep on the tiles covering the region o + [0, e) of the box (the
-// whole box, or a slab along one face); cells of those tiles outside the
-// region are computed too (the same values)
+// the sweep on the tiles covering the whole box (the slab form, a region
+// o + [0, e) along one face, lost its last caller with the overlap schedule:
+// the kernel's origin arguments are always 0)
 template <class T, int TX, int TY, int TZ, int NT>
 static void launch_block(T *u_out, T *u_in, const T *rhs, const T *a, const T *b,
                          const BoxArgs &g, const StencilCoefs &s, bool zero_in, double *acc,
-                         hipStream_t st, const int *o = nullptr, const int *e = nullptr) {
-  const int ox = o ? o[0] : 0, oy = o ? o[1] : 0, oz = o ? o[2] : 0;
-  const int ex = e ? e[0] : g.nx, ey = e ? e[1] : g.ny, ez = e ? e[2] : g.nz;
-  if (ox & 1) throw Error(kBadArg, "block sweep: odd x origin");
-  const int ntx = (ex + TX - 1) / TX, nty = (ey + TY - 1) / TY, ntz = (ez + TZ - 1) / TZ;
+                         hipStream_t st) {
+  const int ntx = (g.nx + TX - 1) / TX, nty = (g.ny + TY - 1) / TY, ntz = (g.nz + TZ - 1) / TZ;
   const int nblocks = ntx * nty * ntz;
   if (nblocks <= 0) return;
   const dim3 grid((unsigned)nblocks), block(NT);
 #define MGIC_BK(Z, B, A)                                                                     \
-  k_gsrb_block<T, TX, TY, TZ, NT, Z, B, A><<<grid, block, 0, st>>>(                          \
-      u_out, acc, u_in, rhs, a, b, g, s, ntx, nty, nblocks, ox, oy, oz)
+  ledger::launch<k_gsrb_block<T, TX, TY, TZ, NT, Z, B, A>>(                                  \
+      grid, block, 0, st, u_out, acc, u_in, rhs, a, b, g, s, ntx, nty, nblocks, 0, 0, 0)
   if (acc) {
     if (zero_in) throw Error(kBadArg, "fused sweep: accumulate on a zero input");
     if (s.bconst) MGIC_BK(false, true, true);
@@ -1132,11 +1130,11 @@ static void launch_fused_rst(double *u_out, double *u_in, const double *rhs, con
   const int nblocks = ntx * nty * ntz;
   const dim3 grid((unsigned)nblocks), block(NT);
   if (s.bconst)
-    k_gsrb_fused_rst<TX, TY, NT, true><<<grid, block, 0, st>>>(u_out, rc, u_in, rhs, a, b, g, s, cg,
-                                                              kc, ntx, nty, nblocks);
+    ledger::launch<k_gsrb_fused_rst<TX, TY, NT, true>>(grid, block, 0, st, u_out, rc, u_in, rhs, a, b,
+                                                       g, s, cg, kc, ntx, nty, nblocks);
   else
-    k_gsrb_fused_rst<TX, TY, NT, false><<<grid, block, 0, st>>>(u_out, rc, u_in, rhs, a, b, g, s, cg,
-                                                               kc, ntx, nty, nblocks);
+    ledger::launch<k_gsrb_fused_rst<TX, TY, NT, false>>(grid, block, 0, st, u_out, rc, u_in, rhs, a,
+                                                        b, g, s, cg, kc, ntx, nty, nblocks);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess)
     throw Error(kHipErr, std::string("fused sweep+restrict launch: ") + hipGetErrorString(e));

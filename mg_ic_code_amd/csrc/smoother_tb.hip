@@ -49,6 +49,7 @@
 #include <type_traits>
 
 #include "kernels.hpp"
+#include "launch_ledger.hpp"
 #include "sweep_util.hpp"
 
 namespace mgic {
@@ -818,15 +819,15 @@ __global__ __launch_bounds__(NT) void k_gsrb_tb2(T *__restrict__ uo,
   const int z0 = (L / (ntx * nty)) * kc;
   const int z1 = min(z0 + kc, g.nz);
   // uniform: the x / y domain faces the tile's rings (3 cells) reach
-  const int ef = (g.bcm[0] && x0 <= 3 ? 1 : 0) | (g.bcm[1] && min(x0 + TX, g.nx) + 3 >= g.nx ? 2 : 0) |
-                 (g.bcm[2] && y0 <= 3 ? 4 : 0) | (g.bcm[3] && min(y0 + TY, g.ny) + 3 >= g.ny ? 8 : 0);
+  const int ef = MGIC_TB2_EDGE_FACES(g, x0, y0, TX, TY);
 #define MGIC_TILE(EM)                                                                             \
   tb2_tile<T, TX, TY, NT, ZIN, ACC, FAST, EM, UBC, TRIM>(RB, uo, acc, ui, rhs, a, g, s, gg, x0, y0,  \
                                                          z0, z1, ef)
   // (uniform) an x-face or a y-face tile runs only that direction's ghost code
+  // (the chain of sweep::tb2_tile_class)
   if (!ef) MGIC_TILE(0);
-  else if (UBC && !(ef & 12)) MGIC_TILE(UBC ? 3 : 15);
-  else if (UBC && !(ef & 3)) MGIC_TILE(UBC ? 12 : 15);
+  else if (MGIC_TB2_X_FACE_TILE(UBC, ef)) MGIC_TILE(UBC ? 3 : 15);
+  else if (MGIC_TB2_Y_FACE_TILE(UBC, ef)) MGIC_TILE(UBC ? 12 : 15);
   else MGIC_TILE(15);
 #undef MGIC_TILE
 }
@@ -939,17 +940,35 @@ void launch_tb2(T *u_out, const T *u_in, const T *rhs, const T *a, const BoxArgs
   const int kind_bit = acc ? 4 : (zero_in ? 1 : 2);
   const bool trim = kDbl && fast && ubc && (trim_mask & kind_bit) &&
                     ((trim_mask & 8) || (double)g.nx * g.ny * g.nz >= kTrimMinCells);
+  // the tile classes this grid contains, for the launch ledger: ef's x bits
+  // depend on the tile column alone and its y bits on the tile row
+  unsigned present = 0;
+  {
+    unsigned xs = 0, ys = 0;  // sets of the x parts (0..3) and y parts (0, 4, 8, 12) / 4
+    for (int tx = 0; tx < ntx; ++tx) xs |= 1u << (sweep::tb2_edge_faces(g, tx * TX, 0, TX, TY) & 3);
+    for (int ty = 0; ty < nty; ++ty)
+      ys |= 1u << ((sweep::tb2_edge_faces(g, 0, ty * TY, TX, TY) & 12) >> 2);
+    for (int fx = 0; fx < 4; ++fx)
+      for (int fy = 0; fy < 4; ++fy)
+        if ((xs >> fx & 1) && (ys >> fy & 1))
+          present |= ledger::class_bit(sweep::tb2_tile_class(ubc, fx | (fy << 2)));
+  }
+  // (the kernel compiles classes 3 and 12 only with UBC)
+  constexpr unsigned kClsUbc = 15, kClsGen = ledger::class_bit(0) | ledger::class_bit(15);
 #define MGIC_TB2(Z, A, FA)                                                                         \
   do {                                                                                             \
     if (ubc && FA && trim)                                                                         \
-      k_gsrb_tb2<T, TX, TY, NT, Z, A, FA, true, FA && kDbl><<<grid, block, 0, st>>>(              \
-          u_out, acc, u_in, rhs, a, g, s, gg, kc, ntx, nty, nblocks, skip, rw);                          \
+      ledger::launch_tiles<k_gsrb_tb2<T, TX, TY, NT, Z, A, FA, true, FA && kDbl>, kClsUbc>(        \
+          present, grid, block, 0, st, u_out, acc, u_in, rhs, a, g, s, gg, kc, ntx, nty, nblocks,  \
+          skip, rw);                                                                               \
     else if (ubc)                                                                                  \
-      k_gsrb_tb2<T, TX, TY, NT, Z, A, FA, true, false><<<grid, block, 0, st>>>(                    \
-          u_out, acc, u_in, rhs, a, g, s, gg, kc, ntx, nty, nblocks, skip, rw);                          \
+      ledger::launch_tiles<k_gsrb_tb2<T, TX, TY, NT, Z, A, FA, true, false>, kClsUbc>(             \
+          present, grid, block, 0, st, u_out, acc, u_in, rhs, a, g, s, gg, kc, ntx, nty, nblocks,  \
+          skip, rw);                                                                               \
     else                                                                                           \
-      k_gsrb_tb2<T, TX, TY, NT, Z, A, FA, false, false><<<grid, block, 0, st>>>(                   \
-          u_out, acc, u_in, rhs, a, g, s, gg, kc, ntx, nty, nblocks, skip, rw);                          \
+      ledger::launch_tiles<k_gsrb_tb2<T, TX, TY, NT, Z, A, FA, false, false>, kClsGen>(            \
+          present, grid, block, 0, st, u_out, acc, u_in, rhs, a, g, s, gg, kc, ntx, nty, nblocks,  \
+          skip, rw);                                                                               \
   } while (0)
   if (acc) {
     if (zero_in) throw Error(kBadArg, "two-sweep launch: accumulate on a zero input");

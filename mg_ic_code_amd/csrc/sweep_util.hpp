@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "mgic_core.hpp"
 
 namespace mgic {
@@ -71,6 +73,32 @@ __device__ __forceinline__ int xcd_tile(int bid, int nblocks) {
   const int q8 = nblocks / 8, r8 = nblocks % 8;
   const int xcd = bid % 8, i8 = bid / 8;
   return xcd * q8 + min(xcd, r8) + i8;
+}
+
+// Two-sweep kernel (smoother_tb.hip): the x / y domain faces the rings (3
+// cells) of the tile at (x0, y0) reach (ef), and the tests on ef that pick
+// the tile class (EM of tb2_tile) the kernel runs.  The kernel and the
+// host's tb2_edge_faces / tb2_tile_class below are the same text, so the
+// launch ledger (launch_ledger.hpp) records the classes a grid contains
+// from the very expressions the kernel dispatches on.  (Macros, not a
+// function the kernel calls: the kernel's code stays what it was.)
+#define MGIC_TB2_EDGE_FACES(g, x0, y0, TX, TY)                                             \
+  (((g).bcm[0] && (x0) <= 3 ? 1 : 0) |                                                     \
+   ((g).bcm[1] && min((x0) + (TX), (g).nx) + 3 >= (g).nx ? 2 : 0) |                        \
+   ((g).bcm[2] && (y0) <= 3 ? 4 : 0) |                                                     \
+   ((g).bcm[3] && min((y0) + (TY), (g).ny) + 3 >= (g).ny ? 8 : 0))
+#define MGIC_TB2_X_FACE_TILE(UBC, ef) ((UBC) && !((ef) & 12))  // class 3
+#define MGIC_TB2_Y_FACE_TILE(UBC, ef) ((UBC) && !((ef) & 3))   // class 12
+inline int tb2_edge_faces(const BoxArgs &g, int x0, int y0, int tx, int ty) {
+  using std::min;
+  return MGIC_TB2_EDGE_FACES(g, x0, y0, tx, ty);
+}
+// (0: interior; without UBC an edge tile of any kind takes the general class 15)
+inline int tb2_tile_class(bool ubc, int ef) {
+  if (!ef) return 0;
+  if (MGIC_TB2_X_FACE_TILE(ubc, ef)) return 3;
+  if (MGIC_TB2_Y_FACE_TILE(ubc, ef)) return 12;
+  return 15;
 }
 
 // Round-major variant (w = workgroups resident per XCD): in each dispatch

@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "kernels.hpp"
+#include "launch_ledger.hpp"
 #include "transport.hpp"
 
 namespace mgic {
@@ -332,9 +333,8 @@ static void exchange_t(const CopyItem *put_items, const CopyItem *loc_items,
   const int n = npu + nlo + nge;
   if (n <= 0) return;
   const int g = grid_cap > 0 && grid_cap < n ? grid_cap : n;  // (the Comm always caps)
-  k_exchange<T><<<dim3((unsigned)g), dim3(256), 0, st>>>(put_items, loc_items, get_items, blocks,
-                                                         npu, nlo, n, src_tab,
-                                                         dst_tab, pput, pget);
+  ledger::launch<k_exchange<T>>(dim3((unsigned)g), dim3(256), 0, st, put_items, loc_items,
+                                get_items, blocks, npu, nlo, n, src_tab, dst_tab, pput, pget);
   check_launch();
 }
 
@@ -355,7 +355,7 @@ void ipc_exchange_f(const CopyItem *put_items, const CopyItem *loc_items,
 
 void ipc_allreduce(double *val, int op, const IpcReduce &r, unsigned long long *err,
                    const HostPub &pub, hipStream_t st) {
-  k_ipc_allreduce<<<1, 64, 0, st>>>(val, op, r, err, pub);
+  ledger::launch<k_ipc_allreduce>(1, 64, 0, st, val, op, r, err, pub);
   check_launch();
 }
 

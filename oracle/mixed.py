@@ -35,8 +35,10 @@ F = np.float32
 
 class MixedOracle:
     def __init__(self, o: "oracle.OracleMG", alpha, beta, bc_lo=(0, 0, 0), bc_hi=(0, 0, 0),
-                 n_pre=4, n_post=4, n_bottom=4):
+                 n_pre=4, n_post=4, n_bottom=4, prolong_type=1):
         assert o.nbox == 1, "single box"
+        assert prolong_type in (0, 1)
+        self.prolong_type = prolong_type  # 0: piecewise constant, 1: linear (the oracle's own)
         self.o = o
         self.D = o.nlevels
         self.n_pre, self.n_post, self.n_bottom = n_pre, n_post, n_bottom
@@ -122,8 +124,16 @@ class MixedOracle:
         return s
 
     def prolong(self, d, e, ec):
-        """e += P ec (linear, one-sided at the domain faces; single box)"""
+        """e += P ec (linear, one-sided at the domain faces, or piecewise
+        constant: every child takes its parent's value; single box)"""
         c = ec[1:-1, 1:-1, 1:-1]
+        if self.prolong_type == 0:
+            f = e[1:-1, 1:-1, 1:-1]
+            for kk in range(2):
+                for jj in range(2):
+                    for ii in range(2):
+                        f[kk::2, jj::2, ii::2] = f[kk::2, jj::2, ii::2] + c
+            return
         nzc, nyc, nxc = c.shape
         out = [None] * 3
         for dd in range(3):  # x, y, z

@@ -41,6 +41,8 @@ def main():
     ap.add_argument("--mode", choices=("vcycle", "mixed"), default="vcycle")
     ap.add_argument("--fmg", type=int, default=0,
                     help="vcycle mode: one fp64 FMG cycle (MultiGrid::fmg) before the iterations")
+    ap.add_argument("--transport", choices=("ipc", "rccl"), default="ipc",
+                    help="rccl: one RCCL communicator over the ranks (its id from rank 0 over gloo)")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
 
@@ -56,7 +58,12 @@ def main():
     dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{a.port}", rank=a.rank,
                             world_size=a.world, timeout=datetime.timedelta(seconds=120))
     mg.set_device(a.device)
-    comm = mg.Comm(a.rank, a.world, transport="ipc")
+    if a.transport == "rccl":
+        uid = [mg.Comm.unique_id() if a.rank == 0 else None]
+        dist.broadcast_object_list(uid, src=0)
+        comm = mg.Comm(a.rank, a.world, unique_id=uid[0])
+    else:
+        comm = mg.Comm(a.rank, a.world, transport="ipc")
     from mg_ic_code_amd.commcheck import check_transport
     checked = check_transport(comm, a.world)  # bench.py's transport check
     mixed = a.mode == "mixed"

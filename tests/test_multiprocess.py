@@ -32,7 +32,7 @@ def free_port():
 
 
 def run_workers(tmp_path, world, n, levels=3, agglomerate_below=0, timeout=240, mode="vcycle",
-                bottom_solver=0, fmg=0, env_extra=None):
+                bottom_solver=0, fmg=0, env_extra=None, transport="ipc", devices=1):
     port = free_port()
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", PYTHONUNBUFFERED="1", **(env_extra or {}))
     procs = []
@@ -44,7 +44,8 @@ def run_workers(tmp_path, world, n, levels=3, agglomerate_below=0, timeout=240, 
             [sys.executable, os.path.join(ROOT, "tests", "mp_worker.py"), "--rank", str(r),
              "--world", str(world), "--port", str(port), "--n", str(n), "--levels", str(levels),
              "--agglomerate-below", str(agglomerate_below), "--out", str(tmp_path),
-             "--mode", mode, "--bottom-solver", str(bottom_solver), "--fmg", str(fmg)],
+             "--mode", mode, "--bottom-solver", str(bottom_solver), "--fmg", str(fmg),
+             "--transport", transport, "--device", str(r % devices)],
             stdout=log, stderr=subprocess.STDOUT, env=env))
     rcs = []
     try:
@@ -83,10 +84,10 @@ def single_box(n, levels, iters=2, mode="vcycle", bottom_solver=0, fmg=0):
     return norms, fphi.download(0)
 
 
-def check(out, n, levels, iters=2, mode="vcycle", bottom_solver=0, fmg=0):
+def check(out, n, levels, iters=2, mode="vcycle", bottom_solver=0, fmg=0, transport="ipc"):
     norms, phi = single_box(n, levels, iters, mode, bottom_solver, fmg)
     for o in out:
-        assert str(o["transport"]) == "ipc"
+        assert str(o["transport"]) == transport
         assert bool(o["checked"])  # commcheck.check_transport passed on every rank
         assert list(o["norms"]) == norms, (list(o["norms"]), norms)
         i = 0
