@@ -56,6 +56,15 @@ bool gsrb_sweep_tb2_applies(const BoxArgs &g, const StencilCoefs &s, int kind);
 void gsrb_sweep_tb2(double *u_out, const double *u_in, const double *rhs, const double *a,
                     const BoxArgs &g, const StencilCoefs &s, bool zero_in, double *acc,
                     hipStream_t st, const int *skip = nullptr);
+// The zero-input launch with the residual it runs on formed inside it: r =
+// rhs - L(phi) under g's ghost rules (written to r's valid cells, bit for bit
+// what residual_norm writes), u_out = two sweeps from zero on r, and max |r|
+// per workgroup into partials[0, gsrb_sweep_tb2_res_blocks(g)).  fp64, boxes
+// with domain faces only, where gsrb_sweep_tb2_applies holds.
+int gsrb_sweep_tb2_res_blocks(const BoxArgs &g);
+void gsrb_sweep_tb2_res(double *u_out, double *r, const double *phi, const double *rhs,
+                        const double *a, const BoxArgs &g, const StencilCoefs &s,
+                        double *partials, hipStream_t st);
 // the same two-sweep launch on fp32 fields; acc (the fp64 phi, or null):
 // the second sweep's values are added to it as (double)e instead of stored
 void gsrb_sweep_tb2_f(float *u_out, const float *u_in, const float *rhs, const float *a,

@@ -411,6 +411,21 @@ static int sweeps_per_launch() {
   return v;
 }
 
+bool VariableCoeffPoissonOperator::fusedResidualApplies(bool homogeneous, int normType, int n) {
+  static const bool on = [] {
+    const char *e = getenv("MGIC_FUSED_RES");
+    return !e || atoi(e) != 0;
+  }();
+  if (!on || (normType != 0 && normType != -1) || n < 2) return false;
+  if (prm.relax_mode != 1 || cf || !fusedSmootherApplies() || sweeps_per_launch() < 2) return false;
+  if (grid->nlocal() != 1 || grid->has_memory_faces()) return false;
+  // the kernel applies the correction's (homogeneous) ghost rules to phi
+  const BoxArgs &h = args_hom_[0], &r = args(0, homogeneous);
+  if (std::memcmp(h.bcm, r.bcm, sizeof h.bcm) != 0 || std::memcmp(h.bcc, r.bcc, sizeof h.bcc) != 0)
+    return false;
+  return kern::gsrb_sweep_tb2_applies(h, coefs(), prm.fused_smoother);
+}
+
 // Deep halo (deep_halo = 1): a 4-deep ghost shell feeds two sweeps.  The
 // first sweeps the box grown by 2 across every exchanged face -- the
 // neighbours' cells within 2 of the face, recomputed from the shell with the
@@ -460,7 +475,8 @@ static BoxArgs grow_exchanged(const BoxArgs &g, int d, long *off) {
 bool VariableCoeffPoissonOperator::fusedRelax(LevelData &dpsi, const LevelData &rhs, int n,
                                               bool zero_in, LevelData *acc, int flags,
                                               LevelData *rst,
-                                              const std::function<void()> *before_acc) {
+                                              const std::function<void()> *before_acc,
+                                              FusedResidual *fr) {
   resetLambda();  // .cpp:283
   const hipStream_t st = stream();
   const StencilCoefs s = coefs();
@@ -545,9 +561,25 @@ bool VariableCoeffPoissonOperator::fusedRelax(LevelData &dpsi, const LevelData &
     for (int b = 0; b < grid->nlocal(); ++b) {
       // the roofline instrumentation times the sweep kernels only (the
       // sweep+restriction launch moves other bytes)
-      const long nc = last && restrict_last ? 0 : grid->geom[b].valid.ncells();
+      const bool res = fr && it == 0;  // the pair also forms its rhs (+ residual)
+      const long nc = (last && restrict_last) || res ? 0 : grid->geom[b].valid.ncells();
       prof_mark(st, nc, true, 2 * k);
-      if (k == 2)  // two sweeps in one launch (temporal blocking), + phi += e
+      if (res) {
+        MGIC_CHECK(zin && k == 2 && !acc && grid->nlocal() == 1,
+                   "fused residual on a relax it does not apply to");
+        check_same_layout(*grid, *fr->phi, "residual dpsi");
+        check_same_layout(*grid, *fr->rhs, "residual rhs");
+        Comm &c = *grid->comm;
+        const int nparts = kern::gsrb_sweep_tb2_res_blocks(args_hom_[b]);
+        double *parts = c.d_partials(nparts);
+        kern::gsrb_sweep_tb2_res(dst->p[b], rhs.p[b], fr->phi->p[b], fr->rhs->p[b], m_aCoef->p[b],
+                                 args_hom_[b], s, parts, st);
+        if (fr->norm) {  // max |r|, as residualNormQueue's
+          finish_reduce(3, parts, nparts, kNormSlot);
+          fr->ticket = c.last_ticket();
+        }
+        fr->done = true;
+      } else if (k == 2)  // two sweeps in one launch (temporal blocking), + phi += e
         kern::gsrb_sweep_tb2(dst->p[b], src->p[b], rhs.p[b], m_aCoef->p[b], args_hom_[b], s, zin,
                              last && acc ? acc->p[b] : nullptr, st);
       else if (last && restrict_last)  // + restrictResidual(rst, result, rhs)
@@ -604,10 +636,11 @@ void VariableCoeffPoissonOperator::relaxFromZero(LevelData &e, const LevelData &
 }
 
 bool VariableCoeffPoissonOperator::relaxRestrict(LevelData &e, const LevelData &r, int n,
-                                                 bool zero_in, int flags, LevelData &resC) {
+                                                 bool zero_in, int flags, LevelData &resC,
+                                                 FusedResidual *fr) {
   if (n > 0 && prm.relax_mode == 1 && fusedSmootherApplies()) {
     resetLambda();
-    return fusedRelax(e, r, n, zero_in, nullptr, flags, &resC);
+    return fusedRelax(e, r, n, zero_in, nullptr, flags, &resC, nullptr, fr);
   }
   if (zero_in)
     relaxFromZero(e, r, n, flags);
@@ -1381,7 +1414,7 @@ void MultiGrid::bottom_solve(VariableCoeffPoissonOperator &op, LevelData &e, Lev
 }
 
 void MultiGrid::cycle(int d, LevelData &e, LevelData &r, bool e_zero, LevelData *phi_acc,
-                      bool halo_out, const std::function<void()> *before_phi) {
+                      bool halo_out, const std::function<void()> *before_phi, FusedResidual *fr) {
   VariableCoeffPoissonOperator &op = *levels_[d].op;
   const hipStream_t st = op.stream();
   // r's ghost layer once per level visit (the fused sweeps' red ring reads
@@ -1412,7 +1445,7 @@ void MultiGrid::cycle(int d, LevelData &e, LevelData &r, bool e_zero, LevelData 
   // restricts in its last sweep
   Level &N = levels_[d + 1];
   LevelData &rc = N.agg ? *N.r_stage : *N.r;
-  if (!op.relaxRestrict(e, r, prm.n_pre, e_zero, rf | kHaloOut, rc)) {
+  if (!op.relaxRestrict(e, r, prm.n_pre, e_zero, rf | kHaloOut, rc, fr)) {
     op.restrictResidual(rc, e, r, false);
   }
   if (N.agg) N.restrict_plan->execute(*op.grid->comm, N.r_stage->d_tab, N.r->d_tab, st);
@@ -1507,11 +1540,37 @@ void AMRMultiGrid::iterations(LevelData &phi, const LevelData &rhs, LevelData &r
     if (norms) norms[pending] = v;
     pending = -1;
   };
+  // Where it is exact (fusedResidualApplies), iteration i's residual and norm
+  // are left to iteration i+1's first launch, which forms them on its way
+  // (kern::gsrb_sweep_tb2_res) -- the same values, so the same bits; that
+  // launch and the norm's final reduction are queued before the first launch
+  // that writes phi, so `take` still finds the norm.  The last iteration's
+  // residual is a launch of its own.
+  const bool fuse = count > 1 && mg.fusedResidualApplies(homogeneous, normType);
   for (int i = 0; i < count; ++i) {
-    mg.oneCycleFromZeroInto(*corr_, resid, phi, &take);
-    take();  // (a V-cycle with no launch to hook)
-    ticket = op0.residualNormQueue(resid, phi, rhs, homogeneous, normType, &now);
-    pending = i;
+    if (fuse && i > 0) {
+      FusedResidual fr;
+      fr.phi = &phi;
+      fr.rhs = &rhs;
+      fr.norm = normType == 0;
+      bool taken = false;
+      const std::function<void()> take_prev = [&] {  // iteration i-1's norm
+        if (taken) return;
+        taken = true;
+        const double v = fr.ticket ? op0.residualNormTake(fr.ticket) : -1.0;
+        if (norms) norms[i - 1] = v;
+      };
+      mg.oneCycleFromZeroInto(*corr_, resid, phi, &take_prev, &fr);
+      if (!fr.done) throw Error(kState, "fused residual: no launch formed it");
+      take_prev();
+    } else {
+      mg.oneCycleFromZeroInto(*corr_, resid, phi, &take);
+      take();  // (a V-cycle with no launch to hook)
+    }
+    if (!fuse || i == count - 1) {
+      ticket = op0.residualNormQueue(resid, phi, rhs, homogeneous, normType, &now);
+      pending = i;
+    }
   }
   take();
 }
@@ -1531,7 +1590,18 @@ void AMRMultiGrid::precondition(LevelData &e, const LevelData &r, int iters) {
   // first cycle runs on r (its ghosts are the only cells it writes); the
   // residual after the last cycle is not needed
   LevelData &r0 = const_cast<LevelData &>(r);
+  // (the later residuals are left to the cycle's first launch where that is
+  // exact: iterations())
+  const bool fuse = iters > 1 && mg.fusedResidualApplies(true, -1);
   for (int i = 0; i < iters; ++i) {
+    if (i > 0 && fuse) {
+      FusedResidual fr;
+      fr.phi = &e;
+      fr.rhs = &r;
+      mg.oneCycleFromZeroInto(*corr_, *pre_resid_, e, nullptr, &fr);
+      if (!fr.done) throw Error(kState, "fused residual: no launch formed it");
+      continue;
+    }
     if (i > 0) op0.residual(*pre_resid_, e, r, true);
     mg.oneCycleFromZeroInto(*corr_, i == 0 ? r0 : *pre_resid_, e);
   }

@@ -42,6 +42,17 @@ struct OpParams {
 // already / wants the result's face ghosts exchanged on return
 enum RelaxFlags { kRhsHaloReady = 1, kHaloOut = 2 };
 
+// A residual left to the relax that runs on it (fusedRelax from zero): the
+// relax's `rhs` field is then an output, rhs - L(phi) under the homogeneous
+// ghost rules, formed inside the first two-sweep launch
+// (kern::gsrb_sweep_tb2_res) instead of by a residual launch before it.
+struct FusedResidual {
+  const LevelData *phi = nullptr, *rhs = nullptr;
+  bool norm = false;              // also queue max |r| into the norm slot ...
+  unsigned long long ticket = 0;  // ... under this ticket (residualNormTake)
+  bool done = false;              // set by the launch that formed the residual
+};
+
 class VariableCoeffPoissonOperator {
  public:
   static int s_maxCoarse;  // [Chombo] AMRPoissonOp::s_maxCoarse
@@ -187,9 +198,17 @@ class VariableCoeffPoissonOperator {
   // rhs) when the fused kernel can (returns whether it did)
   // before_acc: called on the host right before the first launch that writes
   // acc (nothing queued before it changes acc)
+  // fr: rhs is not there yet -- the first launch forms it (FusedResidual;
+  // only where fusedResidualApplies said so, with zero_in and n >= 2)
   bool fusedRelax(LevelData &dpsi, const LevelData &rhs, int n, bool zero_in = false,
                   LevelData *acc = nullptr, int flags = 0, LevelData *rst = nullptr,
-                  const std::function<void()> *before_acc = nullptr);
+                  const std::function<void()> *before_acc = nullptr, FusedResidual *fr = nullptr);
+  // Whether a residual (rhs - L(phi), BC `homogeneous`, norm normType) may be
+  // left to the `n`-sweep relax from zero that follows it: fp64 two-sweep
+  // launches on one box with domain faces only, the residual's ghost rules
+  // those of the correction, and no norm or the max norm (sums have a fixed
+  // order of partials).  MGIC_FUSED_RES=0 turns it off.
+  bool fusedResidualApplies(bool homogeneous, int normType, int n);
   bool deepApplies() const;
   // r's ghosts for the fused sweeps' rings (once per MultiGrid level visit):
   // face layer 1, or the 4-deep shell in deep-halo mode
@@ -208,7 +227,7 @@ class VariableCoeffPoissonOperator {
   // fold it into its last pass, restrictResidual(resC, e, r) -- returns
   // whether the restriction was done (else the caller restricts)
   bool relaxRestrict(LevelData &e, const LevelData &r, int n, bool zero_in, int flags,
-                     LevelData &resC);
+                     LevelData &resC, FusedResidual *fr = nullptr);
 };
 
 // throws kBadArg unless x lives on g's boxes with g's fab geometry
@@ -315,9 +334,17 @@ class MultiGrid {
   }
   // e = 0; oneCycle(e, r); phi += e (e is scratch afterwards); before_phi:
   // called on the host before the first launch that writes phi
+  // fr: r is formed by the cycle's first launch (fusedResidualApplies); fr->done
+  // reports that it was
   void oneCycleFromZeroInto(LevelData &e, const LevelData &r, LevelData &phi,
-                            const std::function<void()> *before_phi = nullptr) {
-    cycle(0, e, const_cast<LevelData &>(r), true, &phi, false, before_phi);
+                            const std::function<void()> *before_phi = nullptr,
+                            FusedResidual *fr = nullptr) {
+    cycle(0, e, const_cast<LevelData &>(r), true, &phi, false, before_phi, fr);
+  }
+  // the residual before a oneCycleFromZeroInto may be left to it
+  bool fusedResidualApplies(bool homogeneous, int normType) {
+    return depths() > 1 && !levels_[1].agg &&
+           levels_[0].op->fusedResidualApplies(homogeneous, normType, prm.n_pre);
   }
   // full multigrid from the residual r at depth 0: r_{d+1} = R(r_d) at every
   // depth, the bottom solve from zero, then per finer depth e_d = P e_{d+1}
@@ -373,7 +400,8 @@ class MultiGrid {
   // e_zero: treat e as zero on entry (it is zeroed or never read);
   // phi_acc: phi += e at the end (at depth 0 folded into the last sweep)
   void cycle(int d, LevelData &e, LevelData &r, bool e_zero, LevelData *phi_acc,
-             bool halo_out = false, const std::function<void()> *before_phi = nullptr);
+             bool halo_out = false, const std::function<void()> *before_phi = nullptr,
+             FusedResidual *fr = nullptr);
   std::vector<Level> levels_;
   bool bt_on_ = false;
   bool bt_filled_ = false;  // a bottom solve has run (bottom_replay's input exists)
@@ -409,7 +437,9 @@ class AMRMultiGrid {
                    bool homogeneous);
   // `count` iterations from the state iteration() / initResidual() leave
   // (resid = rhs - L(phi)); norms[i] = what the i-th iteration() call would
-  // return, bit for bit (the same launches in the same order).  The host
+  // return, bit for bit (the same launches in the same order -- except that,
+  // where MultiGrid::fusedResidualApplies, every residual but the last is
+  // formed inside the next V-cycle's first launch: the same values).  The host
   // reads iteration i's norm while the GPU runs iteration i+1's V-cycle up
   // to its first phi-writing launch, which is queued only after the read --
   // the place a stop test on that norm would decide -- so the GPU does not

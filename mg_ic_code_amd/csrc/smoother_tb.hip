@@ -193,15 +193,41 @@ template <> struct TB2Vec<float> { using type = float2; };
 // compiled in for those; 0: an interior tile); UBC: every x / y domain face
 // of the box has the same ghost rule (one ghost per update instead of one
 // per face; without it EM is 15 and the faces come from ef).
-template <class T, int TX, int TY, int NT, bool ZIN, bool ACC, bool FAST, int EM, bool UBC, bool TRIM>
+//
+// RES (fp64 zero-input launches, selected at run time by a non-null phi): the
+// launch also forms the residual the sweeps run on.  ui is then phi and rhs
+// the equation's right-hand side; r = rhs - L(phi) (VCCOMPUTERES3D, .ChF:
+// 314-333, the expressions of k_residual_zl in the same order) is computed on
+// the update region of plane p + 1 at the end of step p, INTO the load
+// registers that hold that plane's rhs -- the next step makes its coefficient
+// sets from them as ever -- and the tile's own cells of r go to ro, their
+// max |r| to *rmax (one per workgroup).  A zero input needs no ring slot for
+// the planes p + 1 and p - 6, so phi streams through those two: plane q sits
+// in slot q & 7 from step q - 2 (put after the step's first barrier: the
+// slot's last reader is the black phase of step q - 3) until sweep-1 red of
+// step q overwrites it.  Plane p + 1 serves the x / y neighbours; the z
+// neighbours of a lane's pair are the same columns of planes p and p + 2 (a
+// lane's columns alternate with the plane's parity).  Those of plane p + 2
+// are read from the slot just put; of plane p's the black cell is still in
+// its slot (only sweep-1 red has written there) and the red one is kept from
+// the read two steps ago, one register pair per parity.  11 LDS reads per
+// pair.  phi and rhs / aCoef run one step ahead in one register set each, and
+// lambda is made again at each use instead of carried (step), which keeps
+// the body within 128 VGPRs.  The pipeline starts four steps early (their
+// passes fall outside every range).
+template <class T, int TX, int TY, int NT, bool ZIN, bool ACC, bool FAST, int EM, bool UBC, bool TRIM,
+          bool RES = false>
 __device__ __forceinline__ void tb2_tile(T *__restrict__ RB, T *__restrict__ uo, double *__restrict__ acc,
                                          const T *__restrict__ ui,
                                          const T *__restrict__ rhs,
                                          const T *__restrict__ a, const BoxArgs &g,
                                          const StencilCoefs &s64, const TB2Ghosts<T> &gg, int x0,
-                                         int y0, int z0, int z1, int ef) {
+                                         int y0, int z0, int z1, int ef, T *__restrict__ ro = nullptr,
+                                         double *__restrict__ rmax = nullptr) {
   // (ACC: acc is the fp64 sum field whatever T; a float sweep adds (double)e)
   using F = TB2<TX, TY, NT>;
+  static_assert(!RES || (ZIN && !ACC && kPF2 && std::is_same<T, double>::value),
+                "the fused residual is an fp64 zero-input launch");
   using V = typename TB2Vec<T>::type;
   const TB2Coefs<T> s(s64);
   constexpr int PW = F::PW, CP = F::CP, SS = F::SS, UW = F::UW, NRP = F::NRP, NL = F::NL,
@@ -226,7 +252,8 @@ __device__ __forceinline__ void tb2_tile(T *__restrict__ RB, T *__restrict__ uo,
   const int uxlo = g.bcm[0] ? 0 : -3, uxhi = g.bcm[1] ? nx - 1 : nx + 2;
   const int uylo = g.bcm[2] ? 0 : -3, uyhi = g.bcm[3] ? ny - 1 : ny + 2;
   const bool zdl = g.bcm[4] != 0, zdh = g.bcm[5] != 0;
-  const int pstart = z0 - 3, pend = z1 + 3;
+  // (RES: one 4-step group earlier, for the residual of plane z0 - 3)
+  const int pstart = RES ? z0 - 7 : z0 - 3, pend = z1 + 3;
   // the shift s of a lane's row at plane pstart + t is (gsum + y + t) & 1
   const int gsum = g.glo[0] + g.glo[1] + g.glo[2] + x0 + pstart;
   // in-plane offsets are BYTE offsets from the plane's allocated corner
@@ -428,8 +455,10 @@ __device__ __forceinline__ void tb2_tile(T *__restrict__ RB, T *__restrict__ uo,
   constexpr int PF = (kPF2 && !ACC) ? 2 : 1;
   // (SDY: the steady-state step, kSteady above)
   constexpr bool SDY = std::is_same<T, float>::value || ZIN || ACC;
-  T pu0[PF][NL], pu1[PF][NL];
-  T nr0[PF][NP], nr1[PF][NP], na0[PF][NP], na1[PF][NP];
+  // (RES: one step ahead in one register set each, to stay within 128 VGPRs)
+  constexpr int PFR = RES ? 1 : PF;
+  T pu0[PFR][NL], pu1[PFR][NL];
+  T nr0[PFR][NP], nr1[PFR][NP], na0[PFR][NP], na1[PFR][NP];
   // coefficient sets (rhs, alpha*a, lambda): red of planes p .. p-3 (made
   // when the plane's pair arrives, last used by sweep-2 red three steps
   // later), black of planes p-1 .. p-4 (made one step later from rb / ab);
@@ -453,7 +482,7 @@ __device__ __forceinline__ void tb2_tile(T *__restrict__ RB, T *__restrict__ uo,
     const char *pl = decltype(sd)::value ? plane_u(ui, p) : plane(ui, p == zgl ? 0 : p == zgh ? nz - 1 : p);
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
-      if (ZIN) {  // the input is identically +0 (a freshly zeroed correction)
+      if (ZIN && !RES) {  // the input is identically +0 (a freshly zeroed correction)
         pu0[b][i] = 0.0;
         pu1[b][i] = 0.0;
       } else if (NL * NT <= CP || SDY || tid + i * NT < CP) {
@@ -587,6 +616,17 @@ __device__ __forceinline__ void tb2_tile(T *__restrict__ RB, T *__restrict__ uo,
       zm[i] = at(ldsp(Bm, coy[t][i]), NO + RO + PW * ES);
       zp[i] = at(ldsp(Bp, coy[t][i]), NO + RO + PW * ES);
     }
+    if constexpr (RES && ZC == 2) {
+      // (no zero plane was put beyond a z face: its cells are the images of
+      // this pass's own zero input, which is what the put left there)
+      if (!SD && (k == zfl || k == zfh)) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+          if (k == zfl) zm[i] = ghost(gg, 4, (T)0);
+          if (k == zfh) zp[i] = ghost(gg, 5, (T)0);
+        }
+      }
+    }
     if constexpr (EM != 0) {
 #pragma unroll
       for (int i = 0; i < NP; ++i) {
@@ -686,6 +726,112 @@ __device__ __forceinline__ void tb2_tile(T *__restrict__ RB, T *__restrict__ uo,
       sweep::bstore(rs, e, o2);
     }
   };
+  // RES: r = rhs - L(phi) on the update region of plane k (parity t; phi's
+  // plane k in ring slot sk = es(k), plane k + 1 in the next), from the rhs /
+  // aCoef pairs in load-register set b, which take r in rhs's place; the
+  // tile's cells of r -> ro, their max |r| -> nmax (NaN terms keep the running
+  // value: kernels.hip, red_op<3>).  zk1: the black cell's column in the
+  // plane above, read at the call for plane k - 2 (same parity), where it
+  // was the plane above; now it is the plane below.
+  T zk1[2][NP];
+  double nmax = 0.0;  // the identity of max |x|
+#pragma unroll
+  for (int i = 0; i < NP; ++i) zk1[0][i] = zk1[1][i] = 0.0;
+  auto resid = [&](auto tc, auto bc, auto sd, int k, int sk) {
+    constexpr int t = decltype(tc)::value, b = decltype(bc)::value;
+    constexpr bool SD = decltype(sd)::value;
+    if (NP == 1 && wthr > 3) return;  // rows outside the box (kSkipOut)
+    char *const Bk = slot_base(sk), *const Bp = slot_base(eadd(sk, 1));
+    char *const Bm = slot_base(eadd(sk, -1));
+    auto at = [](char *p, unsigned o) -> T { return *reinterpret_cast<const T *>(p + o); };
+    T c0[NP], c1[NP], xm[NP], xp[NP], ym0[NP], yp0[NP], ym1[NP], yp1[NP], zp0[NP], zp1[NP];
+    T zm0[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      char *const a0 = ldsp(Bk, cbm[i]), *const a1 = ldsp(Bk, coy[t][i]);
+      char *const a2 = ldsp(Bp, coy[t][i]);
+      c0[i] = at(a0, ES);       // R[c]: the red cell, the black one's x - 1
+      c1[i] = at(a0, SB + ES);  // B[c]: the black cell, the red one's x + 1
+      xm[i] = at(a0, SB);       // B[c - 1]
+      xp[i] = at(a0, 2 * ES);   // R[c + 1]
+      ym0[i] = at(a1, SB);
+      yp0[i] = at(a1, SB + 2 * PW * ES);
+      ym1[i] = at(a1, ES);
+      yp1[i] = at(a1, ES + 2 * PW * ES);
+      zp0[i] = at(a2, SB + PW * ES);
+      zp1[i] = at(a2, ES + PW * ES);
+      // (the plane below: its black cells are still in its slot, which so far
+      // only sweep-1 red has written; its red ones were kept two steps ago)
+      zm0[i] = at(ldsp(Bm, coy[t][i]), SB + PW * ES);
+    }
+    const bool kin = SD || (k >= z0 && k < z1);  // uniform
+    const int kk = SD ? k : clampi(k, z0, z1 - 1);
+    const __amdgpu_buffer_rsrc_t rs =
+        sweep::store_rsrc(reinterpret_cast<char *>(ro + corner + (long)kk * sz));
+    constexpr unsigned kDrop = sweep::kDrop;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      T xm0 = xm[i], xp0 = c1[i], xm1 = c0[i], xp1 = xp[i];
+      T ya0 = ym0[i], yb0 = yp0[i], ya1 = ym1[i], yb1 = yp1[i];
+      if constexpr (EM != 0) {  // the domain ghosts, as in pass
+        const int f0 = rinf[t][i] & 15, f1 = (rinf[t][i] >> 4) & 15;
+        if constexpr (UBC) {
+          const T g0 = ghost(gg, 0, c0[i]), g1 = ghost(gg, 0, c1[i]);
+          if constexpr ((EM & 3) != 0) {
+            xm0 = (f0 & 1) ? g0 : xm0;
+            xp0 = (f0 & 2) ? g0 : xp0;
+            xm1 = (f1 & 1) ? g1 : xm1;
+            xp1 = (f1 & 2) ? g1 : xp1;
+          }
+          if constexpr ((EM & 12) != 0) {
+            ya0 = (f0 & 4) ? g0 : ya0;
+            yb0 = (f0 & 8) ? g0 : yb0;
+            ya1 = (f1 & 4) ? g1 : ya1;
+            yb1 = (f1 & 8) ? g1 : yb1;
+          }
+        } else {
+          if (ef & 1) xm0 = (f0 & 1) ? ghost(gg, 0, c0[i]) : xm0;
+          if (ef & 2) xp0 = (f0 & 2) ? ghost(gg, 1, c0[i]) : xp0;
+          if (ef & 4) ya0 = (f0 & 4) ? ghost(gg, 2, c0[i]) : ya0;
+          if (ef & 8) yb0 = (f0 & 8) ? ghost(gg, 3, c0[i]) : yb0;
+          if (ef & 1) xm1 = (f1 & 1) ? ghost(gg, 0, c1[i]) : xm1;
+          if (ef & 2) xp1 = (f1 & 2) ? ghost(gg, 1, c1[i]) : xp1;
+          if (ef & 4) ya1 = (f1 & 4) ? ghost(gg, 2, c1[i]) : ya1;
+          if (ef & 8) yb1 = (f1 & 8) ? ghost(gg, 3, c1[i]) : yb1;
+        }
+      }
+      auto cell = [&](T c, T xa, T xb, T ya, T yb, T za, T zb, T rr, T aa) -> T {
+        const T tx = (xb + xa) - (T)2 * c;
+        const T ty = (yb + ya) - (T)2 * c;
+        const T tz = (zb + za) - (T)2 * c;
+        const T lap = (tx + ty) + tz;  // .ChF:320-329
+        if (FAST) {  // alpha 1, beta -1, bCoef 1: x + (-y) == x - y
+          return (rr - aa * c) - lap * s.dxinv;
+        } else {
+          const T res = rr - s.alpha * aa * c;                      // .ChF:314-316
+          return res + lap * s.dxinv * s.beta * s.bval;  // .ChF:331-333
+        }
+      };
+      const T r0 = cell(c0[i], xm0, xp0, ya0, yb0, zm0[i], zp0[i], nr0[b][i], na0[b][i]);
+      const T r1 = cell(c1[i], xm1, xp1, ya1, yb1, zk1[t][i], zp1[i], nr1[b][i], na1[b][i]);
+      zk1[t][i] = zp1[i];
+      nr0[b][i] = r0;
+      nr1[b][i] = r1;
+      const int st = kin ? (rinf[t][i] >> 8) & 3 : 0;
+      const T m0 = (st & 1) ? fabs(r0) : (T)0, m1 = (st & 2) ? fabs(r1) : (T)0;
+      nmax = m0 > nmax ? m0 : nmax;
+      nmax = m1 > nmax ? m1 : nmax;
+      V w;
+      w.x = r0;
+      w.y = r1;
+      const unsigned off = st_off(t, i);
+      const unsigned o4 = st == 3 ? off : kDrop;
+      const unsigned o2 = st == 1 ? off : (st == 2 ? off + (unsigned)sizeof(T) : kDrop);
+      const T e = st == 1 ? r0 : r1;
+      sweep::bstore(rs, w, o4);
+      sweep::bstore(rs, e, o2);
+    }
+  };
   // One pipeline step at plane p (t: its parity relative to pstart; ring
   // slots es(q)), two barriers:
   //   phase A: sweep-1 red of plane p (ring 3), sweep-2 red of plane p-3 (ring 1)
@@ -700,7 +846,7 @@ __device__ __forceinline__ void tb2_tile(T *__restrict__ RB, T *__restrict__ uo,
     // three steps ago, last use), so no register moves between steps
     constexpr int J = decltype(tc)::value, PT = J & 1, PU = PT ^ 1;
     constexpr int J0 = J, J3 = (J + 1) & 3;
-    constexpr int FB = PF == 2 ? (J & 1) : 0;  // in-flight register set consumed / refilled
+    constexpr int FB = PFR == 2 ? (J & 1) : 0;  // in-flight register set consumed / refilled
     using ICF = IC<FB>;
     using SDC = decltype(sd);
     asm volatile("" : "+s"(p));  // opaque: plane-derived values are recomputed, not kept live
@@ -710,20 +856,24 @@ __device__ __forceinline__ void tb2_tile(T *__restrict__ RB, T *__restrict__ uo,
     for (int i = 0; i < NP; ++i) {
       Br[J0][i] = rb[i];
       Ba[J0][i] = FAST ? ab[i] : s.alpha * ab[i];
-      Bl[J0][i] = lam(Ba[J0][i]);
+      if constexpr (!RES) Bl[J0][i] = lam(Ba[J0][i]);
       Rr[J0][i] = reg_copy(nr0[FB][i]);
       Ra[J0][i] = FAST ? reg_copy(na0[FB][i]) : s.alpha * na0[FB][i];
-      Rl[J0][i] = lam(Ra[J0][i]);
+      if constexpr (!RES) Rl[J0][i] = lam(Ra[J0][i]);
       rb[i] = reg_copy(nr1[FB][i]);
       ab[i] = reg_copy(na1[FB][i]);
     }
     const int E0 = es(p);  // this step's slots derive from this one
-    image(p + 1, ICF{}, SDC{});
-    put(eadd(E0, 1), ICF{});
+    if constexpr (!RES) {
+      image(p + 1, ICF{}, SDC{});
+      put(eadd(E0, 1), ICF{});
+    }
     auto fc = [&] {
-      if (PF == 2) fetch_c(PT, p + 2, ICF{}, SDC{});
+      if constexpr (PFR == 2) fetch_c(PT, p + 2, ICF{}, SDC{});
       else fetch_c(PU, p + 1, ICF{}, SDC{});
     };
+    // (RES: plane p + 1's pairs at once -- the step's end makes r of them)
+    if constexpr (RES) fc();
     auto fa = [&] {
       if constexpr (ACC) {
         const char *pl = SDC::value ? plane_u(acc, p - 3) : plane(acc, p - 3);
@@ -738,7 +888,8 @@ __device__ __forceinline__ void tb2_tile(T *__restrict__ RB, T *__restrict__ uo,
       }
     };
     auto fu = [&] {
-      if (PF == 2) fetch_u(PU, p + 3, ICF{}, SDC{});
+      if constexpr (RES) fetch_u(PU, p + 3, ICF{}, SDC{});  // (put at the next step)
+      else if constexpr (PF == 2) fetch_u(PU, p + 3, ICF{}, SDC{});
       else fetch_u(PT, p + 2, ICF{}, SDC{});
     };
     // The step's global loads are issued in three places, not in one burst
@@ -749,29 +900,61 @@ __device__ __forceinline__ void tb2_tile(T *__restrict__ RB, T *__restrict__ uo,
     // first phase, the colour passes queued behind them (DESIGN.md 3,
     // "Spread load issue": 512^3 plain launch -4.5%, 256^3 -6%, V-cycle
     // +2.5%; the stores and other placements measured no better).
-    fu();
+    if constexpr (!RES) fu();
     __syncthreads();
-    pass(IC<(ZIN && kZinShort) ? 1 : 0>{}, SDC{}, true, 3, PT, p, E0, Rr[J0], Ra[J0], Rl[J0]);
-    fc();
-    pass(IC<0>{}, SDC{}, true, 1, PU, p - 3, eadd(E0, -3), Rr[J3], Ra[J3], Rl[J3]);
+    if constexpr (RES) {  // phi's plane p + 2 -> the slot plane p - 6 has left
+      image(p + 2, ICF{}, SDC{});
+      put(eadd(E0, 2), ICF{});
+      fu();
+    }
+    // (RES: lambda is not carried but made again at each use -- the same
+    // operations on the same value -- which frees eight register pairs for
+    // phi; opaque, or the compiler would carry the first result after all)
+    T tl[NP];
+    auto ls = [&](const T(&ca)[NP], const T(&cl)[NP]) -> const T(&)[NP] {
+      if constexpr (!RES) {
+        return cl;
+      } else {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+          T aa = ca[i];
+          asm volatile("" : "+v"(aa));
+          tl[i] = lam(aa);
+        }
+        return tl;
+      }
+    };
+    pass(IC<(ZIN && kZinShort) ? 1 : 0>{}, SDC{}, true, 3, PT, p, E0, Rr[J0], Ra[J0],
+         ls(Ra[J0], Rl[J0]));
+    if constexpr (!RES) fc();
+    pass(IC<0>{}, SDC{}, true, 1, PU, p - 3, eadd(E0, -3), Rr[J3], Ra[J3], ls(Ra[J3], Rl[J3]));
     __syncthreads();
     fa();
-    pass(IC<(ZIN && kZinShort) ? 2 : 0>{}, SDC{}, false, 2, PU, p - 1, eadd(E0, -1), Br[J0], Ba[J0], Bl[J0]);
-    pass(IC<0>{}, SDC{}, false, 0, PT, p - 4, eadd(E0, -4), Br[J3], Ba[J3], Bl[J3]);
+    pass(IC<(ZIN && kZinShort) ? 2 : 0>{}, SDC{}, false, 2, PU, p - 1, eadd(E0, -1), Br[J0], Ba[J0],
+         ls(Ba[J0], Bl[J0]));
+    pass(IC<0>{}, SDC{}, false, 0, PT, p - 4, eadd(E0, -4), Br[J3], Ba[J3], ls(Ba[J3], Bl[J3]));
     store(PT, p - 4, eadd(E0, -4), SDC{});
+    if constexpr (RES) resid(IC<PU>{}, ICF{}, SDC{}, p + 1, eadd(E0, 1));
   };
 
-  fetch_u(1, pstart - 1, IC<0>{}, IC<0>{});
-  image(pstart - 1, IC<0>{}, IC<0>{});
-  put(es(pstart - 1), IC<0>{});
-  fetch_u(0, pstart, IC<0>{}, IC<0>{});
-  image(pstart, IC<0>{}, IC<0>{});
-  put(es(pstart), IC<0>{});
-  fetch_u(1, pstart + 1, IC<0>{}, IC<0>{});
-  fetch_c(0, pstart, IC<0>{}, IC<0>{});
-  if (PF == 2) {
-    fetch_u(0, pstart + 2, IC<PF - 1>{}, IC<0>{});
-    fetch_c(1, pstart + 1, IC<PF - 1>{}, IC<0>{});
+  if constexpr (RES) {
+    // (the first four steps only fill: the residual first counts for plane
+    // z0 - 3, formed at step pstart + 3 from planes put by steps pstart + 1 ..)
+    fetch_u(0, pstart + 2, IC<0>{}, IC<0>{});
+    fetch_c(0, pstart, IC<0>{}, IC<0>{});
+  } else {
+    fetch_u(1, pstart - 1, IC<0>{}, IC<0>{});
+    image(pstart - 1, IC<0>{}, IC<0>{});
+    put(es(pstart - 1), IC<0>{});
+    fetch_u(0, pstart, IC<0>{}, IC<0>{});
+    image(pstart, IC<0>{}, IC<0>{});
+    put(es(pstart), IC<0>{});
+    fetch_u(1, pstart + 1, IC<0>{}, IC<0>{});
+    fetch_c(0, pstart, IC<0>{}, IC<0>{});
+    if (PF == 2) {
+      fetch_u(0, pstart + 2, IC<PF - 1>{}, IC<0>{});
+      fetch_c(1, pstart + 1, IC<PF - 1>{}, IC<0>{});
+    }
   }
   // (up to three steps past pend: their passes and stores fall outside every
   // range test, their loads are clamped)
@@ -790,13 +973,31 @@ __device__ __forceinline__ void tb2_tile(T *__restrict__ RB, T *__restrict__ uo,
     step(IC<2>{}, sd, p + 2);
     step(IC<3>{}, sd, p + 3);
   };
+  // (RES: the fill is a group longer and starts one earlier, so the first
+  // steady group is the same)
   const int ssh = z1 - 7;
   int p = pstart;
   if (SDY) {
-    for (; p < pstart + 8 && p <= pend; p += 4) group(IC<0>{}, p);
+    for (; p < z0 + 5 && p <= pend; p += 4) group(IC<0>{}, p);
     for (; p <= ssh; p += 4) group(IC<1>{}, p);
   }
   for (; p <= pend; p += 4) group(IC<0>{}, p);
+  if constexpr (RES) {
+    // max |r| of the workgroup (an order-free maximum), through the ring
+    for (int o = 32; o > 0; o >>= 1) {
+      const double v = __shfl_xor(nmax, o, 64);
+      nmax = v > nmax ? v : nmax;
+    }
+    __syncthreads();
+    double *const wm = reinterpret_cast<double *>(RB);
+    if ((tid & 63) == 0) wm[tid >> 6] = nmax;
+    __syncthreads();
+    if (tid == 0) {
+      double m = wm[0];
+      for (int w = 1; w < NT / 64; ++w) m = wm[w] > m ? wm[w] : m;
+      *rmax = m;
+    }
+  }
 }
 
 
@@ -809,7 +1010,9 @@ __global__ __launch_bounds__(NT) void k_gsrb_tb2(T *__restrict__ uo,
                                                  const BoxArgs g, const StencilCoefs s,
                                                  const TB2Ghosts<T> gg, int kc, int ntx, int nty,
                                                  int nblocks, const int *__restrict__ skip,
-                                                 int rw) {
+                                                 int rw, const T *__restrict__ phi,
+                                                 T *__restrict__ ro,
+                                                 double *__restrict__ rparts) {
   using F = TB2<TX, TY, NT>;
   __shared__ T RB[F::RING];  // per ring slot: the red element of every pair, then the black
   if (skip && *skip) return;  // a device-side solve has stopped (BicgState::done)
@@ -825,6 +1028,22 @@ __global__ __launch_bounds__(NT) void k_gsrb_tb2(T *__restrict__ uo,
                                                          z0, z1, ef)
   // (uniform) an x-face or a y-face tile runs only that direction's ghost code
   // (the chain of sweep::tb2_tile_class)
+  // (uniform) phi given: the same tile classes with the residual body (RES),
+  // the launch's rhs being the equation's and ro the residual it forms
+  if constexpr (ZIN && !ACC && std::is_same<T, double>::value) {
+    if (phi) {
+#define MGIC_TILE_RES(EM)                                                                         \
+  tb2_tile<T, TX, TY, NT, ZIN, ACC, FAST, EM, UBC, TRIM, true>(RB, uo, acc, phi, rhs, a, g, s, gg, \
+                                                               x0, y0, z0, z1, ef, ro,            \
+                                                               rparts + blockIdx.x)
+      if (!ef) MGIC_TILE_RES(0);
+      else if (MGIC_TB2_X_FACE_TILE(UBC, ef)) MGIC_TILE_RES(UBC ? 3 : 15);
+      else if (MGIC_TB2_Y_FACE_TILE(UBC, ef)) MGIC_TILE_RES(UBC ? 12 : 15);
+      else MGIC_TILE_RES(15);
+#undef MGIC_TILE_RES
+      return;
+    }
+  }
   if (!ef) MGIC_TILE(0);
   else if (MGIC_TB2_X_FACE_TILE(UBC, ef)) MGIC_TILE(UBC ? 3 : 15);
   else if (MGIC_TB2_Y_FACE_TILE(UBC, ef)) MGIC_TILE(UBC ? 12 : 15);
@@ -891,7 +1110,8 @@ constexpr double kTrimMinCells = 160.0 * 160.0 * 160.0;
 template <class T, int TX, int TY, int NT>
 void launch_tb2(T *u_out, const T *u_in, const T *rhs, const T *a, const BoxArgs &g,
                 const StencilCoefs &s, bool zero_in, double *acc, hipStream_t st,
-                const int *skip = nullptr) {
+                const int *skip = nullptr, const T *phi = nullptr, T *ro = nullptr,
+                double *rparts = nullptr) {
   const TB2Geom<T, TX, TY, NT> G(g);
   const int ntx = G.ntx, nty = G.nty, kc = G.kc, nblocks = G.nblocks;
   // the fp32 ACC launch stores into the fp64 phi at twice the float offsets:
@@ -960,16 +1180,18 @@ void launch_tb2(T *u_out, const T *u_in, const T *rhs, const T *a, const BoxArgs
     if (ubc && FA && trim)                                                                         \
       ledger::launch_tiles<k_gsrb_tb2<T, TX, TY, NT, Z, A, FA, true, FA && kDbl>, kClsUbc>(        \
           present, grid, block, 0, st, u_out, acc, u_in, rhs, a, g, s, gg, kc, ntx, nty, nblocks,  \
-          skip, rw);                                                                               \
+          skip, rw, phi, ro, rparts);                                                              \
     else if (ubc)                                                                                  \
       ledger::launch_tiles<k_gsrb_tb2<T, TX, TY, NT, Z, A, FA, true, false>, kClsUbc>(             \
           present, grid, block, 0, st, u_out, acc, u_in, rhs, a, g, s, gg, kc, ntx, nty, nblocks,  \
-          skip, rw);                                                                               \
+          skip, rw, phi, ro, rparts);                                                              \
     else                                                                                           \
       ledger::launch_tiles<k_gsrb_tb2<T, TX, TY, NT, Z, A, FA, false, false>, kClsGen>(            \
           present, grid, block, 0, st, u_out, acc, u_in, rhs, a, g, s, gg, kc, ntx, nty, nblocks,  \
-          skip, rw);                                                                               \
+          skip, rw, phi, ro, rparts);                                                              \
   } while (0)
+  if (phi && (!zero_in || acc || !kDbl || !ro || !rparts))
+    throw Error(kBadArg, "two-sweep launch: the fused residual is an fp64 zero-input launch");
   if (acc) {
     if (zero_in) throw Error(kBadArg, "two-sweep launch: accumulate on a zero input");
     if (fast) MGIC_TB2(false, true, true);
@@ -1009,6 +1231,19 @@ void gsrb_sweep_tb2(double *u_out, const double *u_in, const double *rhs, const 
                     const BoxArgs &g, const StencilCoefs &s, bool zero_in, double *acc,
                     hipStream_t st, const int *skip) {
   launch_tb2<double, 64, 22, 1024>(u_out, u_in, rhs, a, g, s, zero_in, acc, st, skip);
+}
+
+// the zero-input launch with the residual formed inside it (RES in tb2_tile):
+// r = rhs - L(phi) under g's ghost rules, u_out = two sweeps from zero on r,
+// partials[0, gsrb_sweep_tb2_res_blocks(g)) = max |r| per workgroup
+int gsrb_sweep_tb2_res_blocks(const BoxArgs &g) {
+  return TB2Geom<double, 64, 22, 1024>(g).nblocks;
+}
+void gsrb_sweep_tb2_res(double *u_out, double *r, const double *phi, const double *rhs,
+                        const double *a, const BoxArgs &g, const StencilCoefs &s,
+                        double *partials, hipStream_t st) {
+  launch_tb2<double, 64, 22, 1024>(u_out, nullptr, rhs, a, g, s, true, nullptr, st, nullptr, phi, r,
+                                   partials);
 }
 
 // fp32 (the mixed-precision V-cycle's smoother, BASELINE config C5): the same
