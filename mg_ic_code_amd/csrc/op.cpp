@@ -345,6 +345,10 @@ void VariableCoeffPoissonOperator::computeLambda() {
 void VariableCoeffPoissonOperator::setTime(double t) {
   m_time = t;  // .cpp:400-420 (no b-coefficient interpolator is set in this app)
   m_lambdaNeedsResetting = true;
+  // the reference's notification that coefficient data may have changed in
+  // place (its interpolator writes *m_bCoef here): it reads the live fabs
+  // everywhere, so the face ghosts the fused sweep keeps of them are stale too
+  coef_ghosts_ = false;
 }
 
 // An AMR level whose boxes are isolated patches (no box face touches another

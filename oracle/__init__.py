@@ -5,9 +5,10 @@ reference path, see mgic_oracle.h).  Only tests/, __graft_entry__.smoke()
 and bench.py's cpu_baseline leg import this package, and only as the
 checker.  Parity status (mgic_oracle.h header): the ChF kernels
 and the SetLevelData.cpp functions are pinned bit for bit to the compiled
-reference (oracle/reference.py, tests/test_reference_parity.py); the operator's
-C++, the boundary conditions, the tagging and everything restated from Chombo
-remain "parity unpinned".
+reference (oracle/reference.py, tests/test_reference_parity.py), OracleMG's level
+operators and BC fill to the compiled operator class and ParseBC
+(tests/test_reference_operator.py); the tagging and everything restated from
+Chombo remain "parity unpinned".
 
 Arrays are numpy float64 of shape (nz, ny, nx) (i fastest in memory) over
 an explicit box; `Fab(arr, lo)` ties an array to its box's low corner.

@@ -5,9 +5,10 @@
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg.  Parity status
  * (mgic_oracle.h has the list): the ChF kernels and the SetLevelData.cpp
  * functions are pinned bit for bit to the compiled reference
- * (tests/test_reference_parity.py); the C++ of VariableCoeffPoissonOperator
- * .cpp, SetBCs.cpp, SetGrids.cpp, and everything marked [Chombo] (restated
- * from Chombo 3.2) remain "parity unpinned".  Every formula below cites the
+ * (tests/test_reference_parity.py), the level operators to the compiled
+ * VariableCoeffPoissonOperator.cpp and SetBCs.cpp
+ * (tests/test_reference_operator.py); SetGrids.cpp and everything marked
+ * [Chombo] (restated from Chombo 3.2) remain "parity unpinned".  Every formula below cites the
  * reference line it restates.
  *
  * Floating point: compiled with -ffp-contract=off; every expression keeps

@@ -14,10 +14,15 @@
  *   SetLevelDataF.ChF (the four orc_*3d kernels, orc_getlaplacianpsif and its
  *   gradient form) and Source/SetLevelData.cpp with SetBinaryBH.H and
  *   MyPhiFunction.H (orc_nl_coefs, orc_nl_integrand, orc_binary_bh_coefs,
- *   orc_output_vars).
- *   STILL A RESTATEMENT ("parity unpinned"): the C++ of
- *   VariableCoeffPoissonOperator.cpp (levelGSRB's pass order, resetLambda,
- *   restrictResidual's setVal(0), prolongIncrement), SetBCs.cpp, SetGrids.cpp's
+ *   orc_output_vars); and, through tests/test_reference_operator.py, the
+ *   level operators (orc_mg_residual, _apply_op, _precond, _relax,
+ *   _level_gsrb, _level_jacobi, _restrict_residual, orc_lambda, orc_mg_fill_bc)
+ *   to Source/VariableCoeffPoissonOperator.cpp and Source/SetBCs.cpp, compiled
+ *   against oracle/ref/chombo_operator_standin.H -- which itself restates
+ *   Chombo's DiriBC / NeumBC, exchange, AMRPoissonOp::relax's loop and
+ *   FArrayBox arithmetic, so those stay unpinned.
+ *   STILL A RESTATEMENT ("parity unpinned"): the factory's MGnewOp averaging,
+ *   prolongIncrement, SetGrids.cpp's
  *   tagging, PoissonParameters.cpp, WriteOutput.H's file layout, and
  *   everything that lives in Chombo and not in the reference tree (BC fill,
  *   exchange, prolongation, V-cycle, BiCGStab: restated from Chombo 3.2's

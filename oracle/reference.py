@@ -2,10 +2,12 @@
 
 A ctypes binding of oracle/_ref/libmgic_ref.so, which oracle/ref/Makefile
 compiles from a checkout of the reference itself: the seven ChomboFortran
-subroutines (translated by oracle/ref/chf2f.py, compiled by flang) and
+subroutines (translated by oracle/ref/chf2f.py, compiled by flang),
 Source/SetLevelData.cpp with its headers (compiled unmodified against
-oracle/ref/chombo_standin.H).  This is what the oracle's restatement is
-pinned to; nothing here restates arithmetic.
+oracle/ref/chombo_standin.H), and Source/VariableCoeffPoissonOperator.cpp and
+Source/SetBCs.cpp with theirs (compiled unmodified against
+oracle/ref/chombo_operator_standin.H; `Operator` below).  This is what the
+oracle's restatement is pinned to; nothing here restates arithmetic.
 
 Array conventions are those of oracle/__init__.py: numpy float64 of shape
 (nz, ny, nx) over an explicit box (i fastest), `Fab(arr, lo)` ties an array
@@ -76,6 +78,7 @@ class _Params(ctypes.Structure):
 
 _lib = None
 PD, PI, PF, PP = POINTER(c_double), POINTER(c_int), POINTER(_CFab), POINTER(_Params)
+VP = ctypes.c_void_p
 
 
 def lib():
@@ -101,7 +104,28 @@ def lib():
                 ("mgic_ref_set_binary_bh_psi", [PP, PD], c_double),
                 ("mgic_ref_my_phi_function", [PD, c_double, c_double, PD], c_double),
                 ("mgic_ref_num_multigrid_vars", [], c_int),
-                ("mgic_ref_num_grchombo_vars", [], c_int)):
+                ("mgic_ref_num_grchombo_vars", [], c_int),
+                ("mgic_ref_op_create", [c_int, PI, PI, PI, c_double, c_double, c_double, PI, PI,
+                                        c_double], ctypes.c_void_p),
+                ("mgic_ref_op_destroy", [VP], None),
+                ("mgic_ref_op_field", [VP, c_int, c_int], c_int),
+                ("mgic_ref_op_field_set", [VP, c_int, c_int, PD], None),
+                ("mgic_ref_op_field_get", [VP, c_int, c_int, PD], None),
+                ("mgic_ref_op_lambda_get", [VP, c_int, PD], c_int),
+                ("mgic_ref_op_residual", [VP, c_int, c_int, c_int, c_int], None),
+                ("mgic_ref_op_apply_op", [VP, c_int, c_int, c_int], None),
+                ("mgic_ref_op_apply_op_no_boundary", [VP, c_int, c_int], None),
+                ("mgic_ref_op_precond", [VP, c_int, c_int], None),
+                ("mgic_ref_op_relax", [VP, c_int, c_int, c_int], None),
+                ("mgic_ref_op_level_gsrb", [VP, c_int, c_int], None),
+                ("mgic_ref_op_level_jacobi", [VP, c_int, c_int], None),
+                ("mgic_ref_op_restrict_residual", [VP, c_int, c_int, c_int], None),
+                ("mgic_ref_op_set_alpha_beta", [VP, c_double, c_double], None),
+                ("mgic_ref_op_set_coefs", [VP, c_int, c_int, c_double, c_double], None),
+                ("mgic_ref_op_reset_lambda", [VP], None),
+                ("mgic_ref_op_compute_lambda", [VP], None),
+                ("mgic_ref_op_set_time", [VP, c_double], None),
+                ("mgic_ref_parse_bc", [VP, c_int, c_int, c_int], None)):
             f = getattr(L, name)
             f.argtypes, f.restype = args, res
         for name in ("gsrbhelmholtzvc3d_", "vccomputeop3d_", "vccomputeres3d_", "restrictresvc3d_",
@@ -316,3 +340,117 @@ def binary_bh_psi_on_box(bh: dict, lo, hi, dx):
 def my_phi_function(loc, amplitude, wavelength, L) -> float:
     L = (L, L, L) if np.isscalar(L) else L
     return lib().mgic_ref_my_phi_function(_v3(loc), float(amplitude), float(wavelength), _v3(L))
+
+
+# ---------------------------------------------------------------- the operator class
+def _iarr(v):
+    v = [int(x) for x in v]
+    return (c_int * len(v))(*v)
+
+
+class Operator:
+    """The reference's VariableCoeffPoissonOperator on one level of boxes
+    (each lo0 lo1 lo2 hi0 hi1 hi2) over a domain, with ParseBC as its boundary
+    function.  Fields are numbers handed out by `field()`; arrays are
+    (nz, ny, nx) over a box grown by the field's ghost layers.  `aCoef` and
+    `bCoef` are fields like any other: `set_coefs` hands them to the operator,
+    which keeps them by reference, as the reference's factory does."""
+
+    def __init__(self, boxes, domain, dx, alpha=1.0, beta=-1.0, periodic=(0, 0, 0),
+                 bc_lo=(0, 0, 0), bc_hi=(0, 0, 0), bc_value=0.0):
+        self.boxes = [tuple(int(v) for v in b) for b in boxes]
+        self.coarse_boxes = [tuple(v // 2 for v in b) for b in self.boxes]
+        self._ghost = {}
+        self._level = {}
+        self._h = None
+        h = lib().mgic_ref_op_create(len(self.boxes), _iarr([v for b in self.boxes for v in b]),
+                                     _iarr(domain), _iarr(periodic), float(dx), float(alpha),
+                                     float(beta), _iarr(bc_lo), _iarr(bc_hi), float(bc_value))
+        self._h = VP(h)
+
+    def field(self, ghost=1, level=0, values=None):
+        """A new zero field; `values`: one array per box over the valid cells."""
+        f = lib().mgic_ref_op_field(self._h, int(level), int(ghost))
+        self._ghost[f], self._level[f] = int(ghost), int(level)
+        if values is not None:
+            for b, v in enumerate(values):
+                self.set(f, b, v)
+        return f
+
+    def shape(self, f, b, full=False):
+        x = (self.coarse_boxes if self._level[f] else self.boxes)[b]
+        g = self._ghost[f] if full else 0
+        return tuple(x[3 + d] - x[d] + 1 + 2 * g for d in (2, 1, 0))
+
+    def get(self, f, b, full=False):
+        """Valid cells of box b (full: the whole fab, ghosts included)."""
+        out = np.empty(self.shape(f, b, True))
+        lib().mgic_ref_op_field_get(self._h, f, b, out.ctypes.data_as(PD))
+        g = self._ghost[f]
+        return out if full or g == 0 else np.ascontiguousarray(out[g:-g, g:-g, g:-g])
+
+    def set(self, f, b, arr, full=False):
+        """Valid cells of box b, the ghosts kept (full: the whole fab)."""
+        arr = np.asarray(arr, dtype=np.float64)
+        assert arr.shape == self.shape(f, b, full), (arr.shape, self.shape(f, b, full))
+        g = self._ghost[f]
+        if full or g == 0:
+            whole = np.ascontiguousarray(arr)
+        else:
+            whole = self.get(f, b, full=True)
+            whole[g:-g, g:-g, g:-g] = arr
+        lib().mgic_ref_op_field_set(self._h, f, b, whole.ctypes.data_as(PD))
+
+    def lam(self, b):
+        """m_lambda over box b, or None while it is not defined."""
+        x = self.boxes[b]
+        out = np.empty(tuple(x[3 + d] - x[d] + 1 for d in (2, 1, 0)))
+        return out if lib().mgic_ref_op_lambda_get(self._h, b, out.ctypes.data_as(PD)) else None
+
+    def residual(self, lhs, dpsi, rhs, homogeneous=False):
+        lib().mgic_ref_op_residual(self._h, lhs, dpsi, rhs, int(bool(homogeneous)))
+
+    def apply_op(self, lhs, dpsi, homogeneous=False):
+        lib().mgic_ref_op_apply_op(self._h, lhs, dpsi, int(bool(homogeneous)))
+
+    def apply_op_no_boundary(self, lhs, dpsi):
+        lib().mgic_ref_op_apply_op_no_boundary(self._h, lhs, dpsi)
+
+    def precond(self, cor, res):
+        lib().mgic_ref_op_precond(self._h, cor, res)
+
+    def relax(self, e, r, iterations):
+        lib().mgic_ref_op_relax(self._h, e, r, int(iterations))
+
+    def level_gsrb(self, dpsi, rhs):
+        lib().mgic_ref_op_level_gsrb(self._h, dpsi, rhs)
+
+    def level_jacobi(self, dpsi, rhs):
+        lib().mgic_ref_op_level_jacobi(self._h, dpsi, rhs)
+
+    def restrict_residual(self, res_coarse, dpsi, rhs):
+        lib().mgic_ref_op_restrict_residual(self._h, res_coarse, dpsi, rhs)
+
+    def set_alpha_beta(self, alpha, beta):
+        lib().mgic_ref_op_set_alpha_beta(self._h, float(alpha), float(beta))
+
+    def set_coefs(self, a, b, alpha, beta):
+        lib().mgic_ref_op_set_coefs(self._h, a, b, float(alpha), float(beta))
+
+    def reset_lambda(self):
+        lib().mgic_ref_op_reset_lambda(self._h)
+
+    def compute_lambda(self):
+        lib().mgic_ref_op_compute_lambda(self._h)
+
+    def set_time(self, t):
+        lib().mgic_ref_op_set_time(self._h, float(t))
+
+    def parse_bc(self, f, b, homogeneous=False):
+        """ParseBC alone on box b's fab of field f."""
+        lib().mgic_ref_parse_bc(self._h, f, b, int(bool(homogeneous)))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            lib().mgic_ref_op_destroy(self._h)
+            self._h = None

@@ -18,8 +18,8 @@ functions are pinned bit for bit to the compiled reference
   binary_bh64.json  params.txt's 64^3 SetBinaryBH aCoef / rhs at 64 sampled
                   cells (float.hex), psi = 1.
 
-The fourth is written by the COMPILED reference (oracle/reference.py, which
-needs a checkout of the reference and flang) and is skipped, with a notice,
+The last two are written by the COMPILED reference (oracle/reference.py, which
+needs a checkout of the reference and flang) and are skipped, with a notice,
 where that library is not built:
 
   reference_kernels.npz  inputs and the outputs the reference's own Fortran
@@ -28,6 +28,10 @@ where that library is not built:
                   8x6x4 box and on the special-value case (-0.0, subnormal,
                   1e300, Inf, NaN), every level-data function on a 6^3 part
                   of the 16^3 lattice for params.txt's deck and a second one.
+  reference_operator.npz  what the reference's own operator class and ParseBC
+                  wrote for every case of tests/reference_operator_cases.py of
+                  at most 16 cells a side, one array per box and field
+                  written; the inputs are the ones the cases generate.
 
 usage: python tests/golden/make_golden.py
 """
@@ -131,9 +135,22 @@ def reference_kernels():
     assert reference.mayday_count() == 0
 
 
+def reference_operator():
+    from oracle import reference
+    from tests import reference_operator_cases
+    if not reference.build():
+        print("reference_operator.npz NOT regenerated: no reference checkout at",
+              reference.reference_dir(), "and no", reference.LIB)
+        return
+    reference.mayday_reset()
+    np.savez_compressed(reference_operator_cases.FIXTURE, **reference_operator_cases.build_fixture())
+    assert reference.mayday_count() == 0
+
+
 if __name__ == "__main__":
     kernels12()
     vcycle16()
     binary_bh64()
     reference_kernels()
+    reference_operator()
     print("fixtures written to", HERE)
