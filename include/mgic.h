@@ -542,9 +542,10 @@ MGIC_API int mgic_field_solver_vars_punct(mgic_field dpsi, mgic_field rhs, mgic_
  * holes of bh.  With pot all zero and pi NULL or zero they give the bits of
  * the entry points above.  MGIC_EBADARG, before anything is launched, for
  * what the _punct forms refuse, a non-finite pot entry and a pi of another
- * layout.  The momentum constraint's source Pi d_i phi is not solved for, so
- * data with a non-zero Pi and a varying phi_0 violate that constraint by
- * 8 pi G Pi d_i phi; mgic_field_constraints (below) reports the violation. */
+ * layout.  These entry points leave the momentum constraint's source
+ * Pi d_i phi alone: data with a non-zero Pi and a varying phi_0 violate that
+ * constraint by 8 pi G Pi d_i phi.  mgic_field_constraints (below) reports
+ * the violation; the *_ctt forms ("The momentum constraint") remove it. */
 MGIC_API int mgic_field_nl_coefs_matter(mgic_field psi, mgic_field phi, mgic_field acoef,
                                         mgic_field rhs, const double bh[13], int n,
                                         const double *table, mgic_field pi, const double pot[3]);
@@ -596,6 +597,52 @@ MGIC_API int mgic_field_constraint_vars(mgic_field psi, mgic_field phi, int box,
                                         const double bh[13], int npunct, const double *table,
                                         mgic_field pi, const double *pot, double *out,
                                         int out_on_device);
+/* ---- The momentum constraint: the conformal transverse-traceless step.  The
+ * total tensor is Abar_ij = Abar^BY_ij + LW_ij, with LW_ij the longitudinal
+ * piece libmgic_ctt (mgic_ctt.h) forms from the solutions of
+ *   Lap V_i = S_i,   S_i = -(D_j Abar^BY_ij + pow(psi_0,6.0) * 8 pi G Pi D_i phi_0)
+ *   Lap U   = -(1/4) D_k V_k
+ * so that D_j Abar_ij cancels the matter current.  mgic_field_momentum_source
+ * writes S_1, S_2, S_3 on the valid cells of s1, s2, s3 (the launch of
+ * mgic_field_constraints with the psi_0^-6 weight moved onto the source term
+ * and the whole negated; pot is required, pi NULL: Pi = 0).
+ *
+ * The *_ctt forms are the *_matter / constraint entry points of the same name
+ * with abar[6], six stored fields on psi's layout in the order 11, 12, 13,
+ * 22, 23, 33, added to the Bowen-York components wherever Abar_ij is formed:
+ * A2 of the coefficients, the integrand and Ham, d_j Abar_ij of Mom_i, and the
+ * A11..A33 components of mgic_field_grchombo_vars_ctt.  The coefficients, the
+ * integrand and the output read abar at the cell; the constraints also at
+ * its six neighbours, so its ghost layer 1 must be filled.  pot and all six
+ * fields are required (MGIC_EBADARG otherwise, and for a field of another
+ * layout, before anything is launched); with fields of zeros they give the
+ * values of the forms without abar. */
+MGIC_API int mgic_field_momentum_source(mgic_field psi, mgic_field phi, mgic_field s1,
+                                        mgic_field s2, mgic_field s3, const double bh[13], int n,
+                                        const double *table, mgic_field pi, const double pot[3]);
+MGIC_API int mgic_field_nl_coefs_ctt(mgic_field psi, mgic_field phi, mgic_field acoef,
+                                     mgic_field rhs, const double bh[13], int n,
+                                     const double *table, mgic_field pi, const double pot[3],
+                                     const mgic_field *abar);
+MGIC_API int mgic_field_nl_integrand_ctt(mgic_field psi, mgic_field phi, mgic_field out,
+                                         const double bh[13], int n, const double *table,
+                                         mgic_field pi, const double pot[3],
+                                         const mgic_field *abar);
+MGIC_API int mgic_field_grchombo_vars_ctt(mgic_field psi, mgic_field phi, int n, int k0, int nk,
+                                          const double bh[13], int npunct, const double *table,
+                                          mgic_field pi, const double pot[3],
+                                          const mgic_field *abar, double *out,
+                                          int out_on_device);
+MGIC_API int mgic_field_constraints_ctt(mgic_field psi, mgic_field phi, mgic_field ham,
+                                        mgic_field mom1, mgic_field mom2, mgic_field mom3,
+                                        mgic_field ham_abs, const double bh[13], int n,
+                                        const double *table, mgic_field pi, const double pot[3],
+                                        const mgic_field *abar);
+MGIC_API int mgic_field_constraint_vars_ctt(mgic_field psi, mgic_field phi, int box, int k0,
+                                            int nk, const double bh[13], int npunct,
+                                            const double *table, mgic_field pi,
+                                            const double pot[3], const mgic_field *abar,
+                                            double *out, int out_on_device);
 /* the field's layout: domain, periodicity, dx, number of boxes (all ranks),
  * this rank and the job size; box i's extent, owner rank and local index
  * (-1 if not local); a barrier over the field's communicator */

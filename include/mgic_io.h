@@ -116,6 +116,22 @@ MGIC_IO_API int mgic_io_write_final_data_constraints(const char *filename, int n
                                                      const double *pot, int max_level,
                                                      const int *ref_ratio);
 
+/* The final-data writer with the total tensor of the momentum solve (mgic.h,
+ * "The momentum constraint"): abar holds six stored fields per level, level
+ * l's at abar[6 l .. 6 l + 5] in the order 11, 12, 13, 22, 23, 33 on psi[l]'s
+ * layout, added to the Bowen-York tensor in the A11..A33 components (8-13)
+ * through mgic_field_grchombo_vars_ctt.  constraints != 0: components 27-30
+ * carry mgic_field_constraint_vars_ctt of the same sources (the fields' ghost
+ * layer 1 must then be filled), else zeros.  pot and abar are required;
+ * everything else as mgic_io_write_final_data_matter.  A NULL field and one
+ * of another layout are MGIC_EBADARG before the file is created. */
+MGIC_IO_API int mgic_io_write_final_data_ctt(const char *filename, int nlevels,
+                                             const mgic_field *psi, const mgic_field *phi,
+                                             const double bh[13], int npunct, const double *table,
+                                             const mgic_field *pi, const double pot[3],
+                                             const mgic_field *abar, int constraints,
+                                             int max_level, const int *ref_ratio);
+
 /* The same two layouts from host arrays (tests, and callers whose data is
  * already on the host).  kind 0: final data (31 components), 1: solver data
  * (10).  Level l has nbox[l] boxes (6 ints each, all levels concatenated in

@@ -39,8 +39,15 @@ from .constraints import (  # noqa: F401
     set_constraints,
 )
 from .grids import set_grids  # noqa: F401
-from ._lib import IO_LIB_PATH, LIB_PATH, lib  # noqa: F401
+from ._lib import CTT_LIB_PATH, IO_LIB_PATH, LIB_PATH, lib  # noqa: F401
 from .matter import Matter, PiProfile, ScalarPotential  # noqa: F401
+from .momentum import (  # noqa: F401
+    MomentumFields,
+    fill_ghosts,
+    momentum_source,
+    set_longitudinal,
+    solve_vector_potential,
+)
 from .output import output_final_data, output_solver_data  # noqa: F401
 from .phi import PhiProfile  # noqa: F401
 from .punctures import Puncture, PunctureSet  # noqa: F401

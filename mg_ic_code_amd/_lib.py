@@ -239,6 +239,14 @@ SIGNATURES = {
     "mgic_field_constraints": [H, H, H, H, H, H, H, PD, c_int, PD, H, PD],
     "mgic_field_constraint_vars": [H, H, c_int, c_int, c_int, PD, c_int, PD, H, PD, c_void_p,
                                    c_int],
+    "mgic_field_momentum_source": [H, H, H, H, H, PD, c_int, PD, H, PD],
+    "mgic_field_nl_coefs_ctt": [H, H, H, H, PD, c_int, PD, H, PD, PH],
+    "mgic_field_nl_integrand_ctt": [H, H, H, PD, c_int, PD, H, PD, PH],
+    "mgic_field_grchombo_vars_ctt": [H, H, c_int, c_int, c_int, PD, c_int, PD, H, PD, PH, c_void_p,
+                                     c_int],
+    "mgic_field_constraints_ctt": [H, H, H, H, H, H, H, PD, c_int, PD, H, PD, PH],
+    "mgic_field_constraint_vars_ctt": [H, H, c_int, c_int, c_int, PD, c_int, PD, H, PD, PH,
+                                       c_void_p, c_int],
     "mgic_field_layout": [H, PI, PI, PD, PI, PI, PI],
     "mgic_field_box": [H, c_int, PI, PI, PI],
     "mgic_field_barrier": [H],
@@ -351,6 +359,8 @@ IO_SIGNATURES = {
     "mgic_io_write_final_data_matter": [c_char_p, c_int, PH, PH, PD, c_int, PD, PH, PD, c_int, PI],
     "mgic_io_write_final_data_constraints": [c_char_p, c_int, PH, PH, PD, c_int, PD, PH, PD, c_int,
                                              PI],
+    "mgic_io_write_final_data_ctt": [c_char_p, c_int, PH, PH, PD, c_int, PD, PH, PD, PH, c_int,
+                                     c_int, PI],
     "mgic_io_write_host": [c_char_p, c_int, c_int, PI, PI, PI, PD, PI, PD, c_int, c_int],
 }
 _io = None
@@ -375,6 +385,50 @@ def io_call(name: str, *args) -> int:
     st = getattr(L, name)(*args)
     if st < 0:
         msg = L.mgic_io_last_error()
+        raise MgicError(name, st, msg.decode() if msg else "")
+    return st
+
+
+# ---- libmgic_ctt.so (include/mgic_ctt.h): the conformal transverse-traceless
+# kernels of the momentum solve, loaded on first use (momentum.py); missing or
+# unloadable = an ImportError, no fallback
+CTT_LIB_PATH = os.path.join(_HERE, "libmgic_ctt.so")
+CTT_SIGNATURES = {
+    "mgic_ctt_last_error": [],
+    "mgic_ctt_div_rhs": [H, PH, H],
+    "mgic_ctt_w": [H, PH, H, PH],
+    "mgic_ctt_lw": [H, PH, PH],
+    "mgic_ctt_extrap": [H, H],
+    "mgic_ctt_launch_ledger_dump": [c_char_p],
+    "mgic_ctt_launch_ledger_reset": [],
+}
+_ctt = None
+
+
+def ctt_lib() -> ctypes.CDLL:
+    global _ctt
+    if _ctt is None:
+        if not os.path.exists(CTT_LIB_PATH):
+            raise ImportError(f"{CTT_LIB_PATH} not found: build it with __graft_entry__.build()")
+        L = ctypes.CDLL(CTT_LIB_PATH)
+        for name, argtypes in CTT_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.argtypes = argtypes
+            fn.restype = c_char_p if name == "mgic_ctt_last_error" else c_int
+        _ctt = L
+    return _ctt
+
+
+def ctt_loaded() -> bool:
+    """Whether libmgic_ctt.so has been loaded by this process."""
+    return _ctt is not None
+
+
+def ctt_call(name: str, *args) -> int:
+    L = ctt_lib()
+    st = getattr(L, name)(*args)
+    if st < 0:
+        msg = L.mgic_ctt_last_error()
         raise MgicError(name, st, msg.decode() if msg else "")
     return st
 

@@ -26,10 +26,15 @@ and a stored phi_0 are read with their first ghost layer as stored (what the
 integrand needs too); Pi at valid cells only.  Without matter the momentum
 source is the literal zero.
 
-The momentum constraint is not solved for: with a non-zero Pi_0 and a varying
+Without the momentum solve (momentum.py; `poisson_solve(..., momentum=True)`)
+the momentum constraint is not solved for: with a non-zero Pi_0 and a varying
 phi_0 the data violate it by 8 pi G Pi d_i phi, and this module reports by how
-much.  Ham is the residual of the equation the NL loop solves (|dpsi| is only
-its Newton step).
+much.  With it, pass the solve's fields as `momentum=` (or the six stored
+LW_ij of a level as `abar=`): Abar_ij is then the total tensor Abar^BY_ij +
+LW_ij, in A2 of Ham and in d_j Abar_ij of Mom_i, where the stored fields are
+read at the neighbouring cells too (their ghost layer 1 as stored), and what
+remains of Mom_i is truncation error.  Ham is the residual of the equation
+the NL loop solves (|dpsi| is only its Newton step).
 
     set_constraints(psi, out, bh, ...)   one level, into a ConstraintFields
     constraints(psi, prm, ...)           a level or a hierarchy -> ConstraintReport
@@ -49,7 +54,7 @@ import numpy as np
 
 from ._lib import call
 from .core import (AMRSolver, BH_KEYS, Grid, LevelData, OperatorParams, SolverParams)
-from .matter import ScalarPotential, _pot, fill_matter, table_or_null
+from .matter import MatterArgumentError, ScalarPotential, _pot, fill_matter, table_or_null
 from .phi import resolve_phi0
 from .punctures import resolve_punctures
 
@@ -62,6 +67,10 @@ def _bh(bh: dict):
 
 def _h(f: Optional[LevelData]):
     return f.handle if f is not None else None
+
+
+def _handles(fields):
+    return (ctypes.c_void_p * len(fields))(*[f.handle.value for f in fields])
 
 
 def _pot_or_null(potential: Optional[ScalarPotential]):
@@ -86,11 +95,17 @@ class ConstraintFields:
 def set_constraints(psi: LevelData, out: ConstraintFields, bh: dict,
                     potential: Optional[ScalarPotential] = None,
                     pi: Optional[LevelData] = None, punctures=None,
-                    phi: Optional[LevelData] = None) -> None:
+                    phi: Optional[LevelData] = None, abar=None) -> None:
     """Ham, Mom1..3 and Ham_abs of one level at psi, K = bh['constant_K'].
     potential None: no matter (pi must be None); pi None: Pi = 0, else the
     stored Pi_0, which enters Mom_i with the sign it is stored with; punctures
-    None: the deck's two holes; phi None: the analytic Gaussian."""
+    None: the deck's two holes; phi None: the analytic Gaussian; abar: six
+    stored fields (11, 12, 13, 22, 23, 33; ghost layer 1 filled) added to the
+    Bowen-York tensor (needs the potential), None: that tensor alone."""
+    if abar is not None:
+        call("mgic_field_constraints_ctt", _h(psi), _h(phi), *[f.handle for f in out.fields()],
+             _bh(bh), *table_or_null(punctures), _h(pi), _pot_or_null(potential), _handles(abar))
+        return
     call("mgic_field_constraints", _h(psi), _h(phi), *[f.handle for f in out.fields()], _bh(bh),
          *table_or_null(punctures), _h(pi), _pot_or_null(potential))
 
@@ -99,7 +114,7 @@ def constraint_vars(psi: LevelData, n: int, bh: dict, k0: int = 0, nk: Optional[
                     out_device_ptr: Optional[int] = None,
                     potential: Optional[ScalarPotential] = None,
                     pi: Optional[LevelData] = None, punctures=None,
-                    phi: Optional[LevelData] = None) -> Optional[np.ndarray]:
+                    phi: Optional[LevelData] = None, abar=None) -> Optional[np.ndarray]:
     """Ham, Mom1, Mom2, Mom3 for local box n, planes [k0, k0+nk): (4, nk, ny, nx)
     on the host, or written to device memory at out_device_ptr (returns None).
     The sources as in set_constraints."""
@@ -111,6 +126,11 @@ def constraint_vars(psi: LevelData, n: int, bh: dict, k0: int = 0, nk: Optional[
     else:
         out = np.empty((4, nk, ny, nx))
         ptr = out.ctypes.data_as(ctypes.c_void_p)
+    if abar is not None:
+        call("mgic_field_constraint_vars_ctt", _h(psi), _h(phi), n, k0, nk, _bh(bh),
+             *table_or_null(punctures), _h(pi), _pot_or_null(potential), _handles(abar), ptr,
+             int(out_device_ptr is not None))
+        return out
     call("mgic_field_constraint_vars", _h(psi), _h(phi), n, k0, nk, _bh(bh),
          *table_or_null(punctures), _h(pi), _pot_or_null(potential), ptr,
          int(out_device_ptr is not None))
@@ -150,7 +170,7 @@ def _field_norm(x: LevelData, ord: int) -> float:
 
 
 def constraints(psi, prm, phi0=None, punctures=None, matter=None,
-                constant_K: Optional[float] = None) -> ConstraintReport:
+                constant_K: Optional[float] = None, momentum=None) -> ConstraintReport:
     """The constraints of the data at psi (a LevelData, or one per AMR level,
     coarsest first) and their norms.
 
@@ -160,7 +180,10 @@ def constraints(psi, prm, phi0=None, punctures=None, matter=None,
     punctures None -- the deck's table if it has one, else its two holes;
     matter None -- the deck's if it has one, else none.  constant_K: the K of
     the data (a periodic solve's NLResult.constant_K[-1]); None: the dict's
-    own value, 0 for a PoissonParameters.
+    own value, 0 for a PoissonParameters.  momentum: the
+    momentum.MomentumFields of a solve with momentum=True (NLResult.momentum):
+    the constraints of the total tensor Abar^BY_ij + LW_ij; None: of the
+    Bowen-York tensor alone.
 
     On one level the norms are the operator's norm(x, 0) and norm(x, 2) *
     dx^1.5; over a hierarchy AMRSolver.computeNorm, so covered coarse cells
@@ -176,13 +199,16 @@ def constraints(psi, prm, phi0=None, punctures=None, matter=None,
         bh["constant_K"] = float(constant_K)
     punct = resolve_punctures(punctures, prm)
     mat = fill_matter(matter, grids, prm, "constraints")
+    if momentum is not None and mat is None:
+        raise MatterArgumentError("constraints", "momentum= needs the matter of the solve")
     phis = resolve_phi0(phi0, grids, prm)
     rep = ConstraintReport(fields=[ConstraintFields(g) for g in grids])
     for l, f in enumerate(psis):
         set_constraints(f, rep.fields[l], bh,
                         mat.potential if mat is not None else None,
                         mat.level(l) if mat is not None else None, punct,
-                        phis[l] if phis is not None else None)
+                        phis[l] if phis is not None else None,
+                        momentum.lw(l) if momentum is not None else None)
     if len(grids) == 1:
         dx = grids[0].dx
         fs = rep.fields[0].fields()

@@ -651,18 +651,32 @@ static kern::BhParams bh_params(const double bh[13]) {
 // matter: the potential and the Pi_0 handle (the *_matter entry points, which
 // check the coefficients first), or null: rho = 0.
 struct MatterCapi {
-  kern::MatterTerms terms;  // pi unset: box_matter points it at a box
+  kern::MatterTerms terms;  // pi, abar unset: box_matter points them at a box
   mgic_field pi;            // nullable: Pi = 0
+  // the stored tensor added to the Bowen-York Abar_ij (the *_ctt entry points,
+  // which require all six); null: nothing is added
+  mgic_field abar[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 static void check_matter_layout(const Grid &g, const MatterCapi *m) {
   if (m && m->pi) check_same_layout(g, *m->pi->f, "pi");
+  for (int c = 0; m && c < 6; ++c)
+    if (m->abar[c]) check_same_layout(g, *m->abar[c]->f, "abar");
 }
 // box n's terms (null for a null m)
 static const kern::MatterTerms *box_matter(const MatterCapi *m, int n, kern::MatterTerms &box) {
   if (!m) return nullptr;
   box = m->terms;
   box.pi = m->pi ? m->pi->f->p[n] : nullptr;
+  for (int c = 0; c < 6; ++c) box.abar[c] = m->abar[c] ? m->abar[c]->f->p[n] : nullptr;
   return &box;
+}
+// the six fields of a *_ctt entry point, all required
+static void set_abar(MatterCapi &m, const mgic_field *abar) {
+  NEED(abar);
+  for (int c = 0; c < 6; ++c) {
+    MGIC_CHECK(abar[c] != nullptr, "null argument: abar[c]");
+    m.abar[c] = abar[c];
+  }
 }
 static void nl_coefs_capi(mgic_field psi, mgic_field phi, mgic_field acoef, mgic_field rhs,
                           const double bh[13], const kern::PunctureTable *table = nullptr,
@@ -941,6 +955,44 @@ MGIC_API int mgic_field_grchombo_vars_matter(mgic_field psi, mgic_field phi, int
                      &c.m);
   });
 }
+// ---- the *_ctt forms (mgic.h, "The momentum constraint"): the *_matter and
+// constraint entry points with the stored tensor abar[6] (11, 12, 13, 22, 23,
+// 33) added to the Bowen-York Abar_ij; pot and all six fields are required
+MGIC_API int mgic_field_nl_coefs_ctt(mgic_field psi, mgic_field phi, mgic_field acoef,
+                                     mgic_field rhs, const double bh[13], int n,
+                                     const double *table, mgic_field pi, const double pot[3],
+                                     const mgic_field *abar) {
+  return guard([&] {
+    MatterCall c;
+    matter_call(c, n, table, pi, pot);
+    set_abar(c.m, abar);
+    nl_coefs_capi(psi, phi, acoef, rhs, bh, c.table, &c.m);
+  });
+}
+MGIC_API int mgic_field_nl_integrand_ctt(mgic_field psi, mgic_field phi, mgic_field out,
+                                         const double bh[13], int n, const double *table,
+                                         mgic_field pi, const double pot[3],
+                                         const mgic_field *abar) {
+  return guard([&] {
+    MatterCall c;
+    matter_call(c, n, table, pi, pot);
+    set_abar(c.m, abar);
+    psi_generator_capi(kern::constant_k_integrand, psi, phi, out, bh, c.table, &c.m);
+  });
+}
+MGIC_API int mgic_field_grchombo_vars_ctt(mgic_field psi, mgic_field phi, int n, int k0, int nk,
+                                          const double bh[13], int npunct, const double *table,
+                                          mgic_field pi, const double pot[3],
+                                          const mgic_field *abar, double *out,
+                                          int out_on_device) {
+  return guard([&] {
+    MatterCall c;
+    matter_call(c, npunct, table, pi, pot);
+    set_abar(c.m, abar);
+    output_vars_capi(0, psi, nullptr, nullptr, n, k0, nk, bh, out, out_on_device, phi, c.table,
+                     &c.m);
+  });
+}
 // ---- the constraints of the data (mgic.h, "Constraints"): one entry point
 // per job, every optional source nullable.  table null with n = 0: the two
 // holes of bh; pot null: no matter (pi must then be null too); pi null: Pi = 0.
@@ -966,31 +1018,43 @@ static void constraint_call(ConstraintCall &c, int n, const double *table, mgic_
     c.matter = &c.m;
   }
 }
-MGIC_API int mgic_field_constraints(mgic_field psi, mgic_field phi, mgic_field ham,
-                                    mgic_field mom1, mgic_field mom2, mgic_field mom3,
-                                    mgic_field ham_abs, const double bh[13], int n,
-                                    const double *table, mgic_field pi, const double *pot) {
-  return guard([&] {
+// abar null: the Bowen-York tensor alone; source: S_i instead of Mom_i
+static void constraints_capi(mgic_field psi, mgic_field phi, mgic_field ham, mgic_field mom1,
+                             mgic_field mom2, mgic_field mom3, mgic_field ham_abs,
+                             const double bh[13], int n, const double *table, mgic_field pi,
+                             const double *pot, const mgic_field *abar, bool need_abar,
+                             int source) {
+  {
     ConstraintCall c;
     constraint_call(c, n, table, pi, pot);
+    if (need_abar) {
+      NEED(pot);
+      set_abar(c.m, abar);
+    }
     NEED(psi);
-    NEED(ham);
+    if (!source) {  // the source form writes its three components alone
+      NEED(ham);
+      NEED(ham_abs);
+    }
     NEED(mom1);
     NEED(mom2);
     NEED(mom3);
-    NEED(ham_abs);
     NEED(bh);
     const Grid &g = *psi->f->grid;
     const mgic_field out[5] = {ham, mom1, mom2, mom3, ham_abs};
     static const char *const names[5] = {"ham", "mom1", "mom2", "mom3", "ham_abs"};
     for (int a = 0; a < 5; ++a) {
+      if (!out[a]) continue;
       check_same_layout(g, *out[a]->f, names[a]);
       MGIC_CHECK(out[a]->f != psi->f && (!phi || out[a]->f != phi->f) &&
                      (!pi || out[a]->f != pi->f),
                  std::string("aliased argument: ") + names[a] + " is an input");
       for (int b = 0; b < a; ++b)
-        MGIC_CHECK(out[a]->f != out[b]->f,
+        MGIC_CHECK(!out[b] || out[a]->f != out[b]->f,
                    std::string("aliased argument: ") + names[a] + " is " + names[b]);
+      for (int q = 0; q < 6; ++q)
+        MGIC_CHECK(!c.m.abar[q] || out[a]->f != c.m.abar[q]->f,
+                   std::string("aliased argument: ") + names[a] + " is an input");
     }
     if (phi) check_same_layout(g, *phi->f, "phi");
     check_matter_layout(g, c.matter);
@@ -999,21 +1063,58 @@ MGIC_API int mgic_field_constraints(mgic_field psi, mgic_field phi, mgic_field h
     for (int b = 0; b < g.nlocal(); ++b) {
       const BoxArgs a = g.box_args_plain(b);
       kern::ConstraintOut o;
-      for (int q = 0; q < 5; ++q) o.c[q] = out[q]->f->p[b];
+      for (int q = 0; q < 5; ++q) o.c[q] = out[q] ? out[q]->f->p[b] : nullptr;
       o.sy = a.sy;
       o.sz = a.sz;
+      o.source = source;
       kern::constraints(o, psi->f->p[b], phi ? phi->f->p[b] : nullptr, a, 0, a.nz, g.dx, p,
                         g.comm->stream(), c.table, box_matter(c.matter, b, mt));
     }
+  }
+}
+MGIC_API int mgic_field_constraints(mgic_field psi, mgic_field phi, mgic_field ham,
+                                    mgic_field mom1, mgic_field mom2, mgic_field mom3,
+                                    mgic_field ham_abs, const double bh[13], int n,
+                                    const double *table, mgic_field pi, const double *pot) {
+  return guard([&] {
+    constraints_capi(psi, phi, ham, mom1, mom2, mom3, ham_abs, bh, n, table, pi, pot, nullptr,
+                     false, 0);
   });
 }
-MGIC_API int mgic_field_constraint_vars(mgic_field psi, mgic_field phi, int box, int k0, int nk,
-                                        const double bh[13], int npunct, const double *table,
-                                        mgic_field pi, const double *pot, double *out,
-                                        int out_on_device) {
+MGIC_API int mgic_field_constraints_ctt(mgic_field psi, mgic_field phi, mgic_field ham,
+                                        mgic_field mom1, mgic_field mom2, mgic_field mom3,
+                                        mgic_field ham_abs, const double bh[13], int n,
+                                        const double *table, mgic_field pi, const double pot[3],
+                                        const mgic_field *abar) {
   return guard([&] {
+    constraints_capi(psi, phi, ham, mom1, mom2, mom3, ham_abs, bh, n, table, pi, pot, abar, true,
+                     0);
+  });
+}
+// S_i = -(d_j Abar^BY_ij + psi_0^6 * 8 pi G Pi d_i phi) on the valid cells of
+// s1, s2, s3: the right-hand sides of Lap V_i = S_i.  The Hamiltonian
+// components of the launch are not written.
+MGIC_API int mgic_field_momentum_source(mgic_field psi, mgic_field phi, mgic_field s1,
+                                        mgic_field s2, mgic_field s3, const double bh[13], int n,
+                                        const double *table, mgic_field pi,
+                                        const double pot[3]) {
+  return guard([&] {
+    NEED(pot);
+    constraints_capi(psi, phi, nullptr, s1, s2, s3, nullptr, bh, n, table, pi, pot, nullptr,
+                     false, 1);
+  });
+}
+static void constraint_vars_capi(mgic_field psi, mgic_field phi, int box, int k0, int nk,
+                                 const double bh[13], int npunct, const double *table,
+                                 mgic_field pi, const double *pot, const mgic_field *abar,
+                                 bool need_abar, double *out, int out_on_device) {
+  {
     ConstraintCall c;
     constraint_call(c, npunct, table, pi, pot);
+    if (need_abar) {
+      NEED(pot);
+      set_abar(c.m, abar);
+    }
     NEED(psi);
     NEED(bh);
     NEED(out);
@@ -1040,6 +1141,25 @@ MGIC_API int mgic_field_constraint_vars(mgic_field psi, mgic_field phi, int box,
       MGIC_HIP(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, st));
       MGIC_HIP(hipStreamSynchronize(st));
     }
+  }
+}
+MGIC_API int mgic_field_constraint_vars(mgic_field psi, mgic_field phi, int box, int k0, int nk,
+                                        const double bh[13], int npunct, const double *table,
+                                        mgic_field pi, const double *pot, double *out,
+                                        int out_on_device) {
+  return guard([&] {
+    constraint_vars_capi(psi, phi, box, k0, nk, bh, npunct, table, pi, pot, nullptr, false, out,
+                         out_on_device);
+  });
+}
+MGIC_API int mgic_field_constraint_vars_ctt(mgic_field psi, mgic_field phi, int box, int k0,
+                                            int nk, const double bh[13], int npunct,
+                                            const double *table, mgic_field pi,
+                                            const double pot[3], const mgic_field *abar,
+                                            double *out, int out_on_device) {
+  return guard([&] {
+    constraint_vars_capi(psi, phi, box, k0, nk, bh, npunct, table, pi, pot, abar, true, out,
+                         out_on_device);
   });
 }
 MGIC_API int mgic_field_norm(mgic_field x, int ord, double *out) {

@@ -383,11 +383,13 @@ namespace {
 // or one stored Pi_0 field per level, which becomes the component "Pi"
 // constraints: components 27-30 from mgic_field_constraint_vars (a second
 // small launch per slab) instead of set_output_data's zeros
+// abar: null, or six stored fields per level (level l's at abar + 6 l) added
+// to the Bowen-York tensor (the *_ctt entry points; pot is then required)
 int write_final_data(const char *filename, int nlevels, const mgic_field *psi,
                      const mgic_field *phi, const double bh[13], int max_level,
                      const int *ref_ratio, int npunct = 0, const double *table = nullptr,
                      const mgic_field *pi = nullptr, const double *pot = nullptr,
-                     bool constraints = false) {
+                     bool constraints = false, const mgic_field *abar = nullptr) {
   return guard([&] {
     need(psi, "psi");
     need(bh, "bh");
@@ -403,7 +405,11 @@ int write_final_data(const char *filename, int nlevels, const mgic_field *psi,
     for (int l = 0; phi && l < nlevels; ++l) need(phi[l], "phi[l]");
     write_fields(filename ? filename : "vcPoissonFinal.3d.hdf5", J, lead,
                  [&](int l, int n, int k0, int nk, long long plane, double *out) {
-                   if (pot)
+                   if (abar)
+                     mg(mgic_field_grchombo_vars_ctt(psi[l], phi ? phi[l] : nullptr, n, k0, nk, bh,
+                                                     npunct, table, pi ? pi[l] : nullptr, pot,
+                                                     abar + 6 * l, out, 0));
+                   else if (pot)
                      mg(mgic_field_grchombo_vars_matter(psi[l], phi ? phi[l] : nullptr, n, k0, nk,
                                                         bh, npunct, table, pi ? pi[l] : nullptr,
                                                         pot, out, 0));
@@ -414,7 +420,12 @@ int write_final_data(const char *filename, int nlevels, const mgic_field *psi,
                      mg(mgic_field_grchombo_vars_phi(psi[l], phi[l], n, k0, nk, bh, out, 0));
                    else
                      mg(mgic_field_grchombo_vars(psi[l], n, k0, nk, bh, out, 0));
-                   if (constraints)  // Ham, Mom1..3: the slab's last four components
+                   if (constraints && abar)
+                     mg(mgic_field_constraint_vars_ctt(psi[l], phi ? phi[l] : nullptr, n, k0, nk,
+                                                       bh, npunct, table, pi ? pi[l] : nullptr,
+                                                       pot, abar + 6 * l, out + 27 * plane * nk,
+                                                       0));
+                   else if (constraints)  // Ham, Mom1..3: the slab's last four components
                      mg(mgic_field_constraint_vars(psi[l], phi ? phi[l] : nullptr, n, k0, nk, bh,
                                                    npunct, table, pi ? pi[l] : nullptr, pot,
                                                    out + 27 * plane * nk, 0));
@@ -532,7 +543,7 @@ static void check_pi_layout(mgic_field psi, mgic_field pi) {
     ok = owner[0] == owner[1];
     for (int d = 0; ok && d < 6; ++d) ok = lohi[0][d] == lohi[1][d];
   }
-  if (!ok) throw IoError(MGIC_EBADARG, "layout mismatch: pi");
+  if (!ok) throw IoError(MGIC_EBADARG, "layout mismatch: pi or abar");
 }
 
 MGIC_IO_API int mgic_io_write_final_data_matter(const char *filename, int nlevels,
@@ -584,6 +595,39 @@ MGIC_IO_API int mgic_io_write_final_data_constraints(const char *filename, int n
   if (st != MGIC_OK) return st;
   return write_final_data(filename, nlevels, psi, phi, bh, max_level, ref_ratio, npunct, table, pi,
                           pot, true);
+}
+
+// the _matter form's checks, and the six fields of every level
+MGIC_IO_API int mgic_io_write_final_data_ctt(const char *filename, int nlevels,
+                                             const mgic_field *psi, const mgic_field *phi,
+                                             const double bh[13], int npunct, const double *table,
+                                             const mgic_field *pi, const double pot[3],
+                                             const mgic_field *abar, int constraints,
+                                             int max_level, const int *ref_ratio) {
+  const int st = guard([&] {
+    if (table || npunct != 0) check_punctures(npunct, table);
+    need(pot, "pot");
+    for (int c = 0; c < 3; ++c)
+      if (!std::isfinite(pot[c]))
+        throw IoError(MGIC_EBADARG, "potential coefficients (V0, mass, lambda) must be finite");
+    need(psi, "psi");
+    need(abar, "abar");
+    if (nlevels < 1) throw IoError(MGIC_EBADARG, "nlevels < 1");
+    for (int l = 0; l < nlevels; ++l) {
+      need(psi[l], "psi[l]");
+      if (pi) {
+        need(pi[l], "pi[l]");
+        check_pi_layout(psi[l], pi[l]);
+      }
+      for (int c = 0; c < 6; ++c) {
+        need(abar[6 * l + c], "abar[6 l + c]");
+        check_pi_layout(psi[l], abar[6 * l + c]);
+      }
+    }
+  });
+  if (st != MGIC_OK) return st;
+  return write_final_data(filename, nlevels, psi, phi, bh, max_level, ref_ratio, npunct, table, pi,
+                          pot, constraints != 0, abar);
 }
 
 MGIC_IO_API int mgic_io_write_solver_data_punct(const char *filename, int nlevels,

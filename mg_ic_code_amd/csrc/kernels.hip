@@ -1096,6 +1096,23 @@ __device__ __forceinline__ double bh_rho_phi0(const BhParams &p, const double *_
   }
 }
 
+// the stored tensor of the matter (MatterTerms::abar) at offset idx, added to
+// the Bowen-York components; a null abar[0], the same for every lane: nothing
+template <bool MATTER>
+__device__ __forceinline__ void bh_add_abar(BhBowenYork &c, const MatterArg<MATTER> &m,
+                                            long idx) {
+  if constexpr (MATTER) {
+    if (m.m.abar[0]) {
+      c.A11 = c.A11 + m.m.abar[0][idx];
+      c.A12 = c.A12 + m.m.abar[1][idx];
+      c.A13 = c.A13 + m.m.abar[2][idx];
+      c.A22 = c.A22 + m.m.abar[3][idx];
+      c.A23 = c.A23 + m.m.abar[4][idx];
+      c.A33 = c.A33 + m.m.abar[5][idx];
+    }
+  }
+}
+
 // set_a_coef + set_rhs (SetLevelData.cpp:73-127, :281-325); psi == nullptr:
 // psi = 1 everywhere (NL iteration 0), else psi read with its ghost layer
 // INTEGRAND: set_constant_K_integrand (SetLevelData.cpp:131-180) into acoef
@@ -1118,7 +1135,8 @@ __global__ __launch_bounds__(256) void k_binary_bh(double *__restrict__ acoef,
   const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k};
   const long idx = (long)i + (long)j * g.sy + (long)k * g.sz;
   const double rho_grad = bh_rho_grad<STORED>(p, phi, iv, idx, g, dx);
-  const BhBowenYork c = bh_terms<TABLE>(p, t, iv, dx);
+  BhBowenYork c = bh_terms<TABLE>(p, t, iv, dx);
+  bh_add_abar<MATTER>(c, mt, idx);
   const double A2 = bh_A2(c);
   const double rho = bh_rho<MATTER>(mt, bh_rho_phi0<MATTER, STORED>(p, phi, iv, idx, dx), idx);
   const double K = INTEGRAND ? 0.0 : p.constant_K;  // set_m_value(.., 0.0) for the integrand
@@ -1280,8 +1298,9 @@ __global__ __launch_bounds__(256) void k_output_vars(double *__restrict__ out,
   const int k = blockIdx.z;
   if (i >= g.nx || j >= g.ny) return;
   const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k0 + k};
-  const BhBowenYork b = bh_terms<TABLE>(p, t, iv, dx);
+  BhBowenYork b = bh_terms<TABLE>(p, t, iv, dx);
   const long idx = (long)i + (long)j * g.sy + (long)(k0 + k) * g.sz;
+  bh_add_abar<MATTER>(b, mt, idx);
   const double phi0 = bh_phi0<STORED>(p, phi, iv, idx, dx);  // MyPhiFunction.H
   const double psi_c = psi[idx];
   const long V = (long)g.nx * g.ny * nk;
@@ -1335,17 +1354,24 @@ __device__ __forceinline__ double bh_A(const BhBowenYork &c, int i, int j) {
   if (i == j) return i == 0 ? c.A11 : i == 1 ? c.A22 : c.A33;
   return s == 1 ? c.A12 : s == 2 ? c.A13 : c.A23;
 }
+// component (i, j) of the matter's stored tensor (MatterTerms::abar), selected as bh_A
+__device__ __forceinline__ const double *bh_abar(const MatterTerms &m, int i, int j) {
+  const int s = i + j;
+  if (i == j) return i == 0 ? m.abar[0] : i == 1 ? m.abar[3] : m.abar[5];
+  return s == 1 ? m.abar[1] : s == 2 ? m.abar[2] : m.abar[4];
+}
 template <bool STORED, bool TABLE, bool MATTER>
 __device__ __forceinline__ ConstraintCell bh_constraints(
     const double *__restrict__ psi, const double *__restrict__ phi, const int iv[3], long idx,
     const BoxArgs &g, double dx, const BhParams &p, const PunctureArg<TABLE> &t,
-    const MatterArg<MATTER> &mt) {
+    const MatterArg<MATTER> &mt, bool source) {
   const long st[3] = {1, g.sy, g.sz};
   ConstraintCell o;
   const double psi_c = psi[idx];
   double psi_0, A2;
   {
-    const BhBowenYork c = bh_terms<TABLE>(p, t, iv, dx);
+    BhBowenYork c = bh_terms<TABLE>(p, t, iv, dx);
+    bh_add_abar<MATTER>(c, mt, idx);
     A2 = bh_A2(c);
     psi_0 = psi_c + c.psi_bh;
   }
@@ -1377,22 +1403,45 @@ __device__ __forceinline__ ConstraintCell bh_constraints(
   for (int j = 0; j < 3; ++j) {
     const int ip[3] = {iv[0] + (j == 0), iv[1] + (j == 1), iv[2] + (j == 2)};
     const int im[3] = {iv[0] - (j == 0), iv[1] - (j == 1), iv[2] - (j == 2)};
+    // the matter's stored tensor at the two neighbours along j (its ghost layer
+    // 1): three of its components, the pointers selected by j like bh_A
+    bool stored_abar = false;
+    long sj = 0;
+    if constexpr (MATTER) {
+      stored_abar = mt.m.abar[0] != nullptr;
+      sj = j == 0 ? 1 : j == 1 ? g.sy : g.sz;
+    }
     double Ap[3];
     {
       const BhBowenYork c = bh_terms<TABLE>(p, t, ip, dx);
 #pragma unroll
       for (int i = 0; i < 3; ++i) Ap[i] = bh_A(c, i, j);
     }
+    if constexpr (MATTER) {
+      if (stored_abar) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) Ap[i] = Ap[i] + bh_abar(mt.m, i, j)[idx + sj];
+      }
+    }
     const BhBowenYork c = bh_terms<TABLE>(p, t, im, dx);
 #pragma unroll
-    for (int i = 0; i < 3; ++i) divA[i] = divA[i] + 0.5 / dx * (Ap[i] - bh_A(c, i, j));
+    for (int i = 0; i < 3; ++i) {
+      double Am = bh_A(c, i, j);
+      if constexpr (MATTER) {
+        if (stored_abar) Am = Am + bh_abar(mt.m, i, j)[idx - sj];
+      }
+      divA[i] = divA[i] + 0.5 / dx * (Ap[i] - Am);
+    }
   }
   const double w = pow(psi_0, -6.0);
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
     if constexpr (MATTER) {
       const double Pi_field = mt.m.pi ? mt.m.pi[idx] : 0.0;
-      o.mom[i] = w * divA[i] + 8.0 * M_PI * p.G_Newton * Pi_field * dphi[i];
+      if (source)  // S_i of the momentum solve: the weight moves onto the source term
+        o.mom[i] = -(divA[i] + pow(psi_0, 6.0) * (8.0 * M_PI * p.G_Newton * Pi_field * dphi[i]));
+      else
+        o.mom[i] = w * divA[i] + 8.0 * M_PI * p.G_Newton * Pi_field * dphi[i];
     } else {
       o.mom[i] = w * divA[i] + 0.0;  // no matter: the literal zero, as bh_rho
     }
@@ -1418,9 +1467,10 @@ __global__ __launch_bounds__(256) void k_constraints(const ConstraintOut o,
   if (i >= g.nx || j >= g.ny) return;
   const int iv[3] = {g.glo[0] + i, g.glo[1] + j, g.glo[2] + k0 + k};
   const long idx = (long)i + (long)j * g.sy + (long)(k0 + k) * g.sz;
-  const ConstraintCell c = bh_constraints<STORED, TABLE, MATTER>(psi, phi, iv, idx, g, dx, p, t, mt);
+  const ConstraintCell c = bh_constraints<STORED, TABLE, MATTER>(psi, phi, iv, idx, g, dx, p, t, mt,
+                                                                     o.source != 0);
   const long oi = (long)i + (long)j * o.sy + (long)k * o.sz;
-  o.c[0][oi] = c.ham;
+  if (o.c[0]) o.c[0][oi] = c.ham;  // null with o.source: S_i alone
   o.c[1][oi] = c.mom[0];
   o.c[2][oi] = c.mom[1];
   o.c[3][oi] = c.mom[2];
@@ -2334,6 +2384,9 @@ static PunctureArg<true> table_arg(const PunctureTable *t) {
 void check_matter(const MatterTerms &m) {
   if (!std::isfinite(m.V0) || !std::isfinite(m.mass) || !std::isfinite(m.lambda))
     throw Error(kBadArg, "potential coefficients (V0, mass, lambda) must be finite");
+  for (int c = 1; c < 6; ++c)
+    if (!m.abar[c] != !m.abar[0])
+      throw Error(kBadArg, "abar: all six components, or none");
 }
 static MatterArg<true> matter_arg(const MatterTerms *m) {
   MatterArg<true> a;
@@ -2515,9 +2568,10 @@ void constraints(const ConstraintOut &o, const double *psi, const double *phi, c
   check_table(table);
   if (matter) check_matter(*matter);
   if (!psi) throw Error(kBadArg, "null argument: psi");
-  for (int c = 0; c < 4; ++c)
+  for (int c = o.source ? 1 : 0; c < 4; ++c)
     if (!o.c[c]) throw Error(kBadArg, "null argument: constraint output");
   if (k0 < 0 || k0 + nk > g.nz) throw Error(kBadArg, "plane range outside the box");
+  if (o.source && !matter) throw Error(kBadArg, "the momentum source needs the matter");
   if (g.nx <= 0 || g.ny <= 0 || nk <= 0) return;
   if (matter)
     launch_constraints<true>(o, psi, phi, g, k0, nk, dx, p, table, matter_arg(matter), st);

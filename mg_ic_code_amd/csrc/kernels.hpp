@@ -231,10 +231,16 @@ void set_punctures(PunctureTable &t, int n, const double *values);
 // V(phi) = V0 + 0.5 * mass * mass * phi * phi + 0.25 * lambda * phi * phi *
 // phi * phi, evaluated left to right.  pi: the stored Pi_0 of the box, one
 // value per cell on the layout of the other fields (valid cells only are
-// read), or nullptr: Pi = 0.  Passed to the kernels by value.
+// read), or nullptr: Pi = 0.  abar: the six components (11, 12, 13, 22, 23,
+// 33) of a stored tensor added to the Bowen-York Abar_ij wherever the
+// generators form it (the longitudinal piece LW_ij of the momentum solve,
+// include/mgic_ctt.h), on the same layout; all six set, or all null: nothing
+// is added.  The constraints read them at the six neighbours too (ghost layer
+// 1), the other generators at the cell alone.  Passed to the kernels by value.
 struct MatterTerms {
   double V0, mass, lambda;
   const double *pi;
+  const double *abar[6];
 };
 // throws kBadArg on a non-finite coefficient
 void check_matter(const MatterTerms &m);
@@ -288,9 +294,13 @@ void output_vars(int kind, double *out, const double *psi, const double *dpsi, c
 // ghost layer as stored; the Bowen-York terms at the neighbouring cells are
 // evaluated in place.  matter nullptr: the momentum source is the literal
 // zero; its pi (valid cells only) enters Mom_i with the sign it is stored with.
+// source: components 1..3 carry S_i = -(d_j Abar_ij + psi_0^6 * 8 pi G Pi
+// d_i phi) instead of Mom_i, the right-hand side of the momentum solve's
+// Lap V_i = S_i (with matter only).
 struct ConstraintOut {
   double *c[5];
   long sy, sz;
+  int source = 0;
 };
 void constraints(const ConstraintOut &o, const double *psi, const double *phi, const BoxArgs &g,
                  int k0, int nk, double dx, const BhParams &p, hipStream_t st,

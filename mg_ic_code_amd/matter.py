@@ -37,12 +37,14 @@ Only Pi * Pi enters, so the sign of Pi (GRChombo's Pi is "(minus) conjugate
 momentum") is the caller's convention; the final data carry Pi_0 as given in
 component 26.  The solver-data file (the reference's multigrid_vars) has no Pi.
 
-Not done here: the momentum constraint's source Pi d_i phi is not solved for,
-so with a non-zero Pi_0 and a varying phi_0 the data violate that constraint
-by 8 pi G Pi d_i phi.  The violation is reported, not removed: constraints.py
-(`constraints`, `poisson_solve(..., constraints=True)`) gives Ham and Mom_i
-of the data per cell and their norms, and there the sign of Pi does enter.
-No potential beyond this polynomial; no periodic images.
+The momentum constraint: with a non-zero Pi_0 and a varying phi_0 the
+Bowen-York data violate it by 8 pi G Pi d_i phi.  constraints.py
+(`constraints`, `poisson_solve(..., constraints=True)`) reports Ham and Mom_i
+of the data per cell and their norms, and momentum.py
+(`poisson_solve(..., momentum=True)`) removes the violation by the conformal
+transverse-traceless step; in both the sign of Pi does enter.  Without that
+switch the violation stays, as before.
+Not done here: no potential beyond this polynomial; no periodic images.
 Convergence is not guaranteed for large potentials: with constant K the
 operator's aCoef becomes indefinite when V(phi(x)) - <V> outweighs the
 gradient energy.

@@ -47,7 +47,9 @@ from .core import (AMRMultiGrid, AMRSolver, BiCGStabSolver, Grid, LevelData, Mul
 from ._lib import call
 from .constraints import constraints as constraint_report
 from .output import output_final_data, output_solver_data
-from .matter import fill_matter, set_nl_coefs_matter, set_nl_integrand_matter
+from .matter import fill_matter, resolve_matter, set_nl_coefs_matter, set_nl_integrand_matter
+from .momentum import (MomentumFields, MomentumSolver, check_momentum_request, set_longitudinal,
+                       set_nl_coefs_ctt, solve_vector_potential)
 from .params import PoissonParameters
 from .phi import resolve_phi0, set_nl_coefs_phi, set_nl_integrand_phi
 from .punctures import resolve_punctures, set_nl_coefs_punct, set_nl_integrand_punct
@@ -76,6 +78,11 @@ class NLResult:
     converged: bool = False
     constant_K: List[float] = field(default_factory=list)
     constraints: object = None  # constraints.ConstraintReport (poisson_solve(constraints=True))
+    # poisson_solve(momentum=True): the momentum.MomentumFields of the solve (V,
+    # U, W, LW per level), and per NL iteration the BiCGStab iterations of its
+    # four solves (V_x, V_y, V_z, U)
+    momentum: object = None
+    momentum_iterations: List[List[int]] = field(default_factory=list)
 
 
 def set_nl_integrand(psi: LevelData, out: LevelData, bh: dict) -> None:
@@ -84,11 +91,15 @@ def set_nl_integrand(psi: LevelData, out: LevelData, bh: dict) -> None:
     call("mgic_field_nl_integrand", psi.handle, out.handle, vals)
 
 
-def _coefs(psi, phi, a, rhs, bh, punct=None, mat=None, lev=0) -> None:
+def _coefs(psi, phi, a, rhs, bh, punct=None, mat=None, lev=0, mom=None) -> None:
     """set_a_coef + set_rhs: analytic phi_0 (phi None) or the stored field; the
     deck's two holes (punct None) or the puncture table; no matter (mat None:
-    today's calls) or the filled matter's potential and its Pi_0 of level lev."""
-    if mat is not None:
+    today's calls) or the filled matter's potential and its Pi_0 of level lev;
+    mom (with matter): A2 of the total tensor, the momentum fields' LW_ij of
+    level lev added to the Bowen-York one."""
+    if mom is not None:
+        set_nl_coefs_ctt(psi, a, rhs, bh, mat.potential, mom.lw(lev), mat.level(lev), punct, phi)
+    elif mat is not None:
         set_nl_coefs_matter(psi, a, rhs, bh, mat.potential, mat.level(lev), punct, phi)
     elif punct is not None:
         set_nl_coefs_punct(psi, a, rhs, bh, punct, phi=phi)
@@ -113,7 +124,8 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
                   prolong_type: int = 1, bottom_solver: int = 1,
                   max_NL_iterations: Optional[int] = None,
                   output_dir: Optional[str] = None, phi0=None, punctures=None,
-                  matter=None, constraints: bool = False) -> NLResult:
+                  matter=None, constraints: bool = False,
+                  momentum: Optional[bool] = None) -> NLResult:
     """phi0: None -- the analytic Gaussian, evaluated in the kernels; else a
     phi.PhiProfile, or one pre-filled LevelData per level: phi_0 is stored once
     before the NL loop (set_initial_conditions, SetLevelData.cpp:32-71) and the
@@ -129,13 +141,25 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
     constraints: True -- the Hamiltonian and momentum constraints of the
     returned psi (constraints.py), with the solve's own sources and its last K,
     are attached as NLResult.constraints, and the final data carry them in
-    components 27-30.  The solve itself is unchanged."""
+    components 27-30.  The solve itself is unchanged.
+    momentum: True -- the momentum constraint is solved for the matter's
+    Pi d_i phi source (momentum.py): every NL iteration solves for V_i and U,
+    forms the longitudinal piece LW_ij, and takes A2 from the total tensor
+    Abar^BY_ij + LW_ij; the fields are attached as NLResult.momentum, and the
+    constraint report and the final data carry the total tensor.  It needs a
+    matter with a Pi_0 (MatterArgumentError otherwise) and a base that is not
+    periodic (ValueError).  None: the deck's solve_momentum; False: nothing
+    of it is loaded or launched."""
     punct = resolve_punctures(punctures, prm)
+    if momentum is None:
+        momentum = bool(getattr(prm, "solve_momentum", 0))
+    if momentum:  # refused before anything is stored or launched
+        check_momentum_request(resolve_matter(matter, prm), bool(prm.is_periodic))
     if isinstance(grid, (list, tuple)):
         if len(grid) > 1:
             return _poisson_solve_amr(list(grid), prm, max_depth, prolong_type, bottom_solver,
                                       max_NL_iterations, output_dir, phi0, punct, matter,
-                                      constraints)
+                                      constraints, momentum)
         grid = grid[0]
     mat = fill_matter(matter, [grid], prm)
     phis = resolve_phi0(phi0, [grid], prm)
@@ -156,6 +180,13 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
                                relax_mode=1)
     depth = prm.preCondSolverDepth if prm.preCondSolverDepth >= 0 else max_depth
     res = NLResult(psi=psi, dpsi=dpsi)
+    mom = msolve = None
+    if momentum:
+        mom = res.momentum = MomentumFields([grid])
+        msolve = MomentumSolver([grid], prm, op_params, SolverParams(
+            max_depth=depth, n_pre=prm.numMGsmooth, n_post=prm.numMGsmooth,
+            n_bottom=prm.numMGsmooth, bottom_solver=bottom_solver,
+            agglomerate_below=32 if grid.comm.size > 1 else 0))
     n_nl = prm.max_NL_iterations if max_NL_iterations is None else max_NL_iterations
     dx = grid.dx
     ones = integrand = None
@@ -171,7 +202,11 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
             integral = tmp_op.dotProduct(integrand, ones) * dx ** 3  # computeSum
             bh["constant_K"] = -math.sqrt(abs(integral) / volume)
             res.constant_K.append(bh["constant_K"])
-        _coefs(psi, phi, a, rhs, bh, punct, mat)  # :155-161
+        if momentum:  # V_i and U at the current psi, then LW_ij of the total tensor
+            res.momentum_iterations.append(
+                solve_vector_potential(msolve, mom, [psi], bh, mat, punct, phis))
+            set_longitudinal(msolve, mom)
+        _coefs(psi, phi, a, rhs, bh, punct, mat, 0, mom)  # :155-161
         fac = defineOperatorFactory(grid, a, b, op_params)
         # N > 1: depths whose boxes are below 32 cells a side are gathered to
         # one box on rank 0 (the coarsest levels solved on rank 0)
@@ -200,10 +235,10 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
         def write():
             output_final_data([psi], bh, prm.max_level, [2],
                               os.path.join(output_dir, "vcPoissonFinal.3d.hdf5"), phi=phis,
-                              punctures=punct, matter=mat, constraints=constraints)
+                              punctures=punct, matter=mat, constraints=constraints, momentum=mom)
     finish_nl_loop(res, write)
     if constraints:
-        res.constraints = constraint_report(psi, bh, phis, punct, mat)
+        res.constraints = constraint_report(psi, bh, phis, punct, mat, momentum=mom)
     return res
 
 
@@ -217,7 +252,8 @@ def _op_params(prm: PoissonParameters, prolong_type: int) -> OperatorParams:
 def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int,
                        prolong_type: int, bottom_solver: int, max_NL_iterations: Optional[int],
                        output_dir: Optional[str], phi0=None, punct=None,
-                       matter=None, constraints: bool = False) -> NLResult:
+                       matter=None, constraints: bool = False,
+                       momentum: bool = False) -> NLResult:
     """poissonSolve over nlevels = len(grids) AMR levels (Main_PoissonSolver.cpp:51-250)."""
     periodic = bool(prm.is_periodic)
     if periodic != all(grids[0].periodic):
@@ -242,6 +278,10 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
                       n_bottom=prm.numMGsmooth, bottom_solver=bottom_solver,
                       agglomerate_below=32 if grids[0].comm.size > 1 else 0)
     res = NLResult(psi=psi, dpsi=dpsi)
+    mom = msolve = None
+    if momentum:
+        mom = res.momentum = MomentumFields(grids)
+        msolve = MomentumSolver(grids, prm, op_params, sp)
     n_nl = prm.max_NL_iterations if max_NL_iterations is None else max_NL_iterations
     volume = prm.domainLength[0] * prm.domainLength[1] * prm.domainLength[2]
     integrand = geom = None
@@ -258,8 +298,12 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
             integral = geom.computeSum(integrand)
             bh["constant_K"] = -math.sqrt(abs(integral) / volume)
             res.constant_K.append(bh["constant_K"])
+        if momentum:  # V_i and U at the current psi, then LW_ij of the total tensor
+            res.momentum_iterations.append(
+                solve_vector_potential(msolve, mom, psi, bh, mat, punct, phis))
+            set_longitudinal(msolve, mom)
         for l in range(nlev):  # :154-160
-            _coefs(psi[l], phi[l], a[l], rhs[l], bh, punct, mat, l)
+            _coefs(psi[l], phi[l], a[l], rhs[l], bh, punct, mat, l, mom)
         amr = AMRSolver(list(zip(grids, a, b)), op_params, sp)  # :163-170
         solver = BiCGStabSolver(MultilevelLinearOp(amr, prm.numMGIterations),
                                 tolerance=prm.tolerance, max_iterations=prm.max_iterations,
@@ -283,10 +327,10 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
         def write():
             output_final_data(psi, bh, nlev - 1, refs,
                               os.path.join(output_dir, "vcPoissonFinal.3d.hdf5"), phi=phis,
-                              punctures=punct, matter=mat, constraints=constraints)
+                              punctures=punct, matter=mat, constraints=constraints, momentum=mom)
     finish_nl_loop(res, write)
     if constraints:
-        res.constraints = constraint_report(psi, bh, phis, punct, mat)
+        res.constraints = constraint_report(psi, bh, phis, punct, mat, momentum=mom)
     return res
 
 

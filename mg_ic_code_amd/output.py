@@ -27,7 +27,7 @@ import numpy as np
 
 from ._lib import call, io_call
 from .core import BH_KEYS, LevelData
-from .matter import fill_matter, table_or_null
+from .matter import MatterArgumentError, fill_matter, table_or_null
 from .punctures import table_args
 
 GRCHOMBO_VARS = (  # GRChomboUserVariables.hpp:58-75
@@ -54,7 +54,7 @@ def output_final_data(psi: Sequence[LevelData], bh: dict, max_level: int = 0,
                       ref_ratio: Optional[Sequence[int]] = None,
                       filename: Optional[str] = None,
                       phi: Optional[Sequence[LevelData]] = None, punctures=None,
-                      matter=None, constraints: bool = False) -> None:
+                      matter=None, constraints: bool = False, momentum=None) -> None:
     """output_final_data (WriteOutput.H:127-227); constant_K = bh['constant_K'].
     filename None: "vcPoissonFinal.3d.hdf5" in the working directory.
     phi: the stored phi_0 per level (None: the analytic Gaussian).
@@ -65,9 +65,22 @@ def output_final_data(psi: Sequence[LevelData], bh: dict, max_level: int = 0,
     caller's convention.
     constraints: components 27-30 (Ham, Mom1..3) carry the constraints of the
     data (constraints.py; Pi enters Mom_i with the sign it is stored with)
-    instead of set_output_data's zeros; nothing else in the file changes."""
+    instead of set_output_data's zeros; nothing else in the file changes.
+    momentum: the momentum.MomentumFields of a solve with momentum=True (needs
+    the matter): A11..A33, and with `constraints` Ham and Mom1..3, carry the
+    total tensor Abar^BY_ij + LW_ij."""
     n = len(psi)
     rr = list(ref_ratio) if ref_ratio is not None else [2] * n
+    if momentum is not None:
+        mat = fill_matter(matter, [f.grid for f in psi], bh, "output_final_data")
+        if mat is None:
+            raise MatterArgumentError("output_final_data", "momentum= needs the matter of the solve")
+        io_call("mgic_io_write_final_data_ctt", _enc(filename), n, _handles(psi),
+                _handles(phi) if phi is not None else None, _bh(bh), *table_or_null(punctures),
+                _handles(mat.pi) if mat.pi is not None else None, mat.potential.pot(),
+                _handles([f for l in range(n) for f in momentum.lw(l)]), int(bool(constraints)),
+                int(max_level), (ctypes.c_int * n)(*rr))
+        return
     if constraints:
         mat = None
         if matter is not None:
@@ -125,7 +138,7 @@ def output_solver_data(dpsi: Sequence[LevelData], rhs: Sequence[LevelData],
 def grchombo_vars(psi: LevelData, n: int, bh: dict, k0: int = 0, nk: Optional[int] = None,
                   out_device_ptr: Optional[int] = None,
                   phi: Optional[LevelData] = None, punctures=None,
-                  matter=None, constraints: bool = False) -> Optional[np.ndarray]:
+                  matter=None, constraints: bool = False, abar=None) -> Optional[np.ndarray]:
     """set_output_data for local box n, planes [k0, k0+nk): (31, nk, ny, nx) on
     the host, or written to device memory at out_device_ptr (returns None).
     phi: the stored phi_0 (None: the analytic Gaussian).
@@ -133,9 +146,12 @@ def grchombo_vars(psi: LevelData, n: int, bh: dict, k0: int = 0, nk: Optional[in
     matter: a matter.Matter (None: today's calls): component 26, "Pi", is its
     stored Pi_0 as given (the sign is the caller's convention).
     constraints: components 27-30 (Ham, Mom1..3) are filled by a second launch
-    into the same array (constraints.py) instead of left at zero."""
+    into the same array (constraints.py) instead of left at zero.
+    abar: six stored fields (11, 12, 13, 22, 23, 33) of psi's level added to
+    the Bowen-York tensor in A11..A33 and, with `constraints`, in Ham and
+    Mom1..3 (needs the matter; momentum.MomentumFields.lw(level))."""
     return _vars(0, psi, None, None, n, bh, k0, nk, out_device_ptr, phi, punctures, matter,
-                 constraints)
+                 constraints, abar)
 
 
 def solver_vars(dpsi: LevelData, rhs: LevelData, psi: LevelData, n: int, bh: dict, k0: int = 0,
@@ -146,7 +162,7 @@ def solver_vars(dpsi: LevelData, rhs: LevelData, psi: LevelData, n: int, bh: dic
 
 
 def _vars(kind, psi, dpsi, rhs, n, bh, k0, nk, dev, phi=None, punctures=None, matter=None,
-          constraints=False):
+          constraints=False, abar=None):
     lo, hi = psi.grid.local_box(n)[:3], psi.grid.local_box(n)[3:]
     nx, ny, nz = (hi[d] - lo[d] + 1 for d in range(3))
     nk = nz - k0 if nk is None else nk
@@ -158,7 +174,14 @@ def _vars(kind, psi, dpsi, rhs, n, bh, k0, nk, dev, phi=None, punctures=None, ma
         ptr = out.ctypes.data_as(ctypes.c_void_p)
     hphi = phi.handle if phi is not None else None
     mat = None
-    if matter is not None:  # kind 0 only
+    if abar is not None and matter is None:
+        raise MatterArgumentError("grchombo_vars", "abar= needs the matter of the solve")
+    if abar is not None:  # kind 0 only
+        mat = fill_matter(matter, [psi.grid], bh, "grchombo_vars")
+        call("mgic_field_grchombo_vars_ctt", psi.handle, hphi, n, k0, nk, _bh(bh),
+             *table_or_null(punctures), mat.pi[0].handle if mat.pi is not None else None,
+             mat.potential.pot(), _handles(abar), ptr, int(dev is not None))
+    elif matter is not None:  # kind 0 only
         mat = fill_matter(matter, [psi.grid], bh, "grchombo_vars")
         call("mgic_field_grchombo_vars_matter", psi.handle, hphi, n, k0, nk, _bh(bh),
              *table_or_null(punctures), mat.pi[0].handle if mat.pi is not None else None,
@@ -183,6 +206,11 @@ def _vars(kind, psi, dpsi, rhs, n, bh, k0, nk, dev, phi=None, punctures=None, ma
     if constraints:  # kind 0 only: Ham, Mom1..3 are the array's last four components
         slab = 8 * 27 * nk * ny * nx
         cptr = ctypes.c_void_p((dev if dev is not None else out.ctypes.data) + slab)
+        if abar is not None:
+            call("mgic_field_constraint_vars_ctt", psi.handle, hphi, n, k0, nk, _bh(bh),
+                 *table_or_null(punctures), mat.pi[0].handle if mat.pi is not None else None,
+                 mat.potential.pot(), _handles(abar), cptr, int(dev is not None))
+            return out
         call("mgic_field_constraint_vars", psi.handle, hphi, n, k0, nk, _bh(bh),
              *table_or_null(punctures),
              mat.pi[0].handle if mat is not None and mat.pi is not None else None,

@@ -68,6 +68,9 @@ class PoissonParameters:
     # pi_amplitude: a constant Pi; matter.py): the keys the deck gives, by
     # name; None: no matter
     matter: Optional[dict] = None
+    # solve_momentum = 0|1 (not a key of the reference): 1 solves the momentum
+    # constraint for the matter's Pi d_i phi source (momentum.py); absent: 0
+    solve_momentum: int = 0
 
     def bh(self, constant_K: float = 0.0) -> dict:
         """Inputs of set_a_coef / set_rhs (domain length of direction 0)."""
@@ -152,6 +155,11 @@ def read_params(text: str, overrides: Optional[Dict[str, str]] = None) -> Poisso
     matter = {k: v for k, v in matter.items() if v is not None}
     if matter:
         p.matter = matter
+    sm = get("solve_momentum", int, required=False)
+    if sm is not None:
+        if sm not in (0, 1):
+            raise ValueError(f"solve_momentum must be 0 or 1, got {sm}")
+        p.solve_momentum = sm
     return p
 
 

@@ -28,11 +28,15 @@ With --constraints the Hamiltonian and momentum constraints of the solved data
 component (Ham, Mom1, Mom2, Mom3) with its max norm and its L2 norm, then
 max|Ham| / max Ham_abs.
 
+With --momentum (or the deck's solve_momentum = 1) the momentum constraint is
+solved for the matter's Pi d_i phi source (mg_ic_code_amd/momentum.py): needs
+a matter with a Pi, and a base that is not periodic.
+
 usage: python tools/run_poisson.py [params.txt] [--size N] [--boxes-per-rank x,y,z]
                                    [--max-level K] [--phi gaussian|sine]
                                    [--puncture "m x y z Px Py Pz Jx Jy Jz"]...
                                    [--potential "V0 mass lambda"] [--pi VALUE]
-                                   [--constraints]
+                                   [--constraints] [--momentum]
 """
 import argparse
 import json
@@ -63,6 +67,8 @@ def main():
                     help="a constant field velocity Pi; overrides the deck's pi_amplitude")
     ap.add_argument("--constraints", action="store_true",
                     help="report the constraint norms of the solved data")
+    ap.add_argument("--momentum", action="store_true",
+                    help="solve the momentum constraint for the matter's Pi d_i phi source")
     args = ap.parse_args()
     import mg_ic_code_amd as mg
     from mg_ic_code_amd.decomposition import decompose
@@ -106,11 +112,15 @@ def main():
             print(f"level {lev}: {len(g.boxes)} boxes, {cells} cells")
     t0 = time.perf_counter()
     res = poisson_solve(levels, prm, max_depth=args.max_depth, phi0=phi0, punctures=punct,
-                        matter=matter, constraints=args.constraints)
+                        matter=matter, constraints=args.constraints,
+                        momentum=True if args.momentum else None)
     mg.device_synchronize()
     dt = time.perf_counter() - t0
     for i, (nrm, it) in enumerate(zip(res.dpsi_norms, res.linear_iterations)):
         print(f"Main Loop Iteration {i + 1}: {it} BiCGStab iterations, norm of dpsi {nrm:.6e}")
+    for i, its in enumerate(res.momentum_iterations):
+        print(f"Main Loop Iteration {i + 1}: momentum solves V1 V2 V3 U: "
+              + " ".join(str(v) for v in its) + " BiCGStab iterations")
     if args.constraints:
         for line in res.constraints.lines():
             print(line)
@@ -125,6 +135,8 @@ def main():
         out["dpsi_norms"] = res.dpsi_norms
         out["linear_iterations"] = res.linear_iterations
         out["constant_K"] = res.constant_K
+    if res.momentum is not None:
+        out["momentum_iterations"] = res.momentum_iterations
     print(json.dumps(out))
 
 
