@@ -72,6 +72,33 @@ class PoissonParameters:
     # constraint for the matter's Pi d_i phi source (momentum.py); absent: 0
     solve_momentum: int = 0
 
+    # what getPoissonParameters derives besides (PoissonParameters.cpp:68, :78-79,
+    # :111-128): one more level than max_level, ratio 2 on every level, the
+    # domain from the origin, one periodicity flag for every direction
+    @property
+    def numLevels(self) -> int:
+        return self.max_level + 1
+
+    @property
+    def refRatio(self) -> List[int]:
+        return [2] * self.numLevels
+
+    @property
+    def probLo(self) -> List[float]:
+        return [0.0, 0.0, 0.0]
+
+    @property
+    def probHi(self) -> List[float]:
+        return [0.0 + v for v in self.domainLength]
+
+    @property
+    def coarsestDomain(self) -> tuple:
+        return (0, 0, 0) + tuple(n - 1 for n in self.N)
+
+    @property
+    def periodic(self) -> List[int]:
+        return [self.is_periodic] * 3
+
     def bh(self, constant_K: float = 0.0) -> dict:
         """Inputs of set_a_coef / set_rhs (domain length of direction 0)."""
         return dict(domain_length=self.domainLength[0], G_Newton=self.G_Newton,

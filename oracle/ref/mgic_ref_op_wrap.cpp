@@ -13,37 +13,24 @@
  * The reference keeps the boundary flags in process-wide statics
  * (GlobalBCRS) that it parses once; every entry point here first installs
  * the calling operator's flags and value and clears s_areBCsParsed, so
- * several operators with different tables can be alive at once.
+ * several operators with different tables can be alive at once.  An operator
+ * the reference's factory made (mgic_ref_factory_wrap.cpp) arrives in the same
+ * handle and is driven by the same entry points.
  */
-#include "chombo_operator_standin.H"
-
-#include "SetBCs.H"
-#include "VariableCoeffPoissonOperator.H"
+#include "mgic_ref_op_handle.H"
 
 namespace {
 
 mgic_ref_parm g_parm;
 
-typedef LevelData<FArrayBox> Field;
-
-/* levelGSRB and levelJacobi are protected in the reference's class */
-struct Op : VariableCoeffPoissonOperator {
-  using VariableCoeffPoissonOperator::levelGSRB;
-  using VariableCoeffPoissonOperator::levelJacobi;
-};
+typedef mgic_ref_field Field;
+typedef mgic_ref_op_class Op;
 
 } // namespace
 
 extern "C" {
 
 mgic_ref_parm *mgic_ref_parm_table(void) { return &g_parm; }
-
-struct mgic_ref_op {
-  Op op;
-  DisjointBoxLayout fine, coarse; /* coarse: every box coarsened by 2 */
-  mgic_ref_parm parm;
-  std::vector<RefCountedPtr<Field>> fields;
-};
 
 } /* extern "C" */
 
@@ -89,12 +76,15 @@ mgic_ref_op *mgic_ref_op_create(int nbox, const int *boxes, const int *domain, c
   }
   o->parm.bc_value = bc_value;
   /* what the reference's factory sets on a new operator */
-  o->op.m_dx = dx;
-  o->op.m_dxCrse = 2.0 * dx;
-  o->op.m_alpha = alpha;
-  o->op.m_beta = beta;
-  o->op.m_domain = pd;
-  o->op.m_bc = BCHolder(ParseBC);
+  o->op = new Op;
+  o->op->m_exchangeCopier.exchangeDefine(o->fine, IntVect::Unit);
+  o->op->m_exchangeCopier.trimEdges(o->fine, IntVect::Unit);
+  o->op->m_dx = dx;
+  o->op->m_dxCrse = 2.0 * dx;
+  o->op->m_alpha = alpha;
+  o->op->m_beta = beta;
+  o->op->m_domain = pd;
+  o->op->m_bc = BCHolder(ParseBC);
   return o;
 }
 
@@ -122,69 +112,69 @@ void mgic_ref_op_field_get(mgic_ref_op *o, int f, int box, double *dst) {
 
 /* m_lambda's fab of one box (no ghosts); returns 0 while m_lambda is undefined */
 int mgic_ref_op_lambda_get(mgic_ref_op *o, int box, double *dst) {
-  if (!o->op.m_lambda.isDefined()) return 0;
-  const FArrayBox &fab = o->op.m_lambda[DataIndex{box}];
+  if (!o->op->m_lambda.isDefined()) return 0;
+  const FArrayBox &fab = o->op->m_lambda[DataIndex{box}];
   std::memcpy(dst, fab.dataPtr(), sizeof(double) * (size_t)fab.box().numPts());
   return 1;
 }
 
 void mgic_ref_op_residual(mgic_ref_op *o, int lhs, int dpsi, int rhs, int homogeneous) {
   activate(o);
-  o->op.residualI(F(o, lhs), F(o, dpsi), F(o, rhs), homogeneous != 0);
+  o->op->residualI(F(o, lhs), F(o, dpsi), F(o, rhs), homogeneous != 0);
 }
 
 void mgic_ref_op_apply_op(mgic_ref_op *o, int lhs, int dpsi, int homogeneous) {
   activate(o);
-  o->op.applyOpI(F(o, lhs), F(o, dpsi), homogeneous != 0);
+  o->op->applyOpI(F(o, lhs), F(o, dpsi), homogeneous != 0);
 }
 
 void mgic_ref_op_apply_op_no_boundary(mgic_ref_op *o, int lhs, int dpsi) {
   activate(o);
-  o->op.applyOpNoBoundary(F(o, lhs), F(o, dpsi));
+  o->op->applyOpNoBoundary(F(o, lhs), F(o, dpsi));
 }
 
 void mgic_ref_op_precond(mgic_ref_op *o, int cor, int res) {
   activate(o);
-  o->op.preCond(F(o, cor), F(o, res));
+  o->op->preCond(F(o, cor), F(o, res));
 }
 
 void mgic_ref_op_relax(mgic_ref_op *o, int e, int r, int iterations) {
   activate(o);
-  o->op.relax(F(o, e), F(o, r), iterations);
+  o->op->relax(F(o, e), F(o, r), iterations);
 }
 
 void mgic_ref_op_level_gsrb(mgic_ref_op *o, int dpsi, int rhs) {
   activate(o);
-  o->op.levelGSRB(F(o, dpsi), F(o, rhs));
+  o->op->levelGSRB(F(o, dpsi), F(o, rhs));
 }
 
 void mgic_ref_op_level_jacobi(mgic_ref_op *o, int dpsi, int rhs) {
   activate(o);
-  o->op.levelJacobi(F(o, dpsi), F(o, rhs));
+  o->op->levelJacobi(F(o, dpsi), F(o, rhs));
 }
 
 void mgic_ref_op_restrict_residual(mgic_ref_op *o, int res_coarse, int dpsi, int rhs) {
   activate(o);
-  o->op.restrictResidual(F(o, res_coarse), F(o, dpsi), F(o, rhs));
+  o->op->restrictResidual(F(o, res_coarse), F(o, dpsi), F(o, rhs));
 }
 
 void mgic_ref_op_set_alpha_beta(mgic_ref_op *o, double alpha, double beta) {
-  o->op.setAlphaAndBeta(alpha, beta);
+  o->op->setAlphaAndBeta(alpha, beta);
 }
 
 void mgic_ref_op_set_coefs(mgic_ref_op *o, int a, int b, double alpha, double beta) {
-  o->op.setCoefs(o->fields[a], o->fields[b], alpha, beta);
+  o->op->setCoefs(o->fields[a], o->fields[b], alpha, beta);
 }
 
-void mgic_ref_op_reset_lambda(mgic_ref_op *o) { o->op.resetLambda(); }
-void mgic_ref_op_compute_lambda(mgic_ref_op *o) { o->op.computeLambda(); }
-void mgic_ref_op_set_time(mgic_ref_op *o, double t) { o->op.setTime(t); }
+void mgic_ref_op_reset_lambda(mgic_ref_op *o) { o->op->resetLambda(); }
+void mgic_ref_op_compute_lambda(mgic_ref_op *o) { o->op->computeLambda(); }
+void mgic_ref_op_set_time(mgic_ref_op *o, double t) { o->op->setTime(t); }
 
 /* ParseBC alone on one box's fab of a field */
 void mgic_ref_parse_bc(mgic_ref_op *o, int f, int box, int homogeneous) {
   activate(o);
   Field &u = F(o, f);
-  ParseBC(u[DataIndex{box}], u.disjointBoxLayout()[DataIndex{box}], o->op.m_domain, o->op.m_dx,
+  ParseBC(u[DataIndex{box}], u.disjointBoxLayout()[DataIndex{box}], o->op->m_domain, o->op->m_dx,
           homogeneous != 0);
 }
 

@@ -5,8 +5,11 @@ compiles from a checkout of the reference itself: the seven ChomboFortran
 subroutines (translated by oracle/ref/chf2f.py, compiled by flang),
 Source/SetLevelData.cpp with its headers (compiled unmodified against
 oracle/ref/chombo_standin.H), and Source/VariableCoeffPoissonOperator.cpp and
-Source/SetBCs.cpp with theirs (compiled unmodified against
-oracle/ref/chombo_operator_standin.H; `Operator` below).  This is what the
+Source/SetBCs.cpp with theirs (`Operator` below), and
+Source/VariableCoeffPoissonOperatorFactory.cpp, Source/SetGrids.cpp and
+Source/PoissonParameters.cpp (`Factory`, `tag_cells`, `domains_and_dx`,
+`poisson_parameters`), all compiled unmodified against
+oracle/ref/chombo_operator_standin.H.  This is what the
 oracle's restatement is pinned to; nothing here restates arithmetic.
 
 Array conventions are those of oracle/__init__.py: numpy float64 of shape
@@ -76,6 +79,20 @@ class _Params(ctypes.Structure):
         "bh1_spin", "bh2_spin", "bh1_momentum", "bh2_momentum", "bh1_offset", "bh2_offset")]
 
 
+class _PoissonParameters(ctypes.Structure):
+    _fields_ = ([("nCells", c_int * 3), ("maxGridSize", c_int), ("blockFactor", c_int),
+                 ("bufferSize", c_int), ("fillRatio", c_double), ("refineThresh", c_double),
+                 ("coefficient_average_type", c_int), ("verbosity", c_int), ("maxLevel", c_int),
+                 ("numLevels", c_int), ("n_periodic", c_int), ("periodic", c_int * 8),
+                 ("n_refRatio", c_int), ("refRatio", c_int * 32), ("domain", c_int * 6),
+                 ("domain_periodic", c_int * 3), ("coarsestDx", c_double),
+                 ("domainLength", c_double * 3), ("probLo", c_double * 3), ("probHi", c_double * 3)] +
+                [(k, c_double) for k in (
+                    "alpha", "beta", "G_Newton", "phi_amplitude", "phi_wavelength", "bh1_bare_mass",
+                    "bh2_bare_mass", "bh1_spin", "bh2_spin", "bh1_momentum", "bh2_momentum",
+                    "bh1_offset", "bh2_offset")])
+
+
 _lib = None
 PD, PI, PF, PP = POINTER(c_double), POINTER(c_int), POINTER(_CFab), POINTER(_Params)
 VP = ctypes.c_void_p
@@ -125,7 +142,30 @@ def lib():
                 ("mgic_ref_op_reset_lambda", [VP], None),
                 ("mgic_ref_op_compute_lambda", [VP], None),
                 ("mgic_ref_op_set_time", [VP, c_double], None),
-                ("mgic_ref_parse_bc", [VP, c_int, c_int, c_int], None)):
+                ("mgic_ref_parse_bc", [VP, c_int, c_int, c_int], None),
+                ("mgic_ref_last_error", [], ctypes.c_char_p),
+                ("mgic_ref_deck_clear", [], None),
+                ("mgic_ref_deck_add", [ctypes.c_char_p, ctypes.c_char_p], None),
+                ("mgic_ref_get_poisson_parameters", [POINTER(_PoissonParameters)], c_int),
+                ("mgic_ref_set_domains_and_dx", [c_int, PI, PI, c_double, PI, PI, PI, PD], c_int),
+                ("mgic_ref_set_tag_cells", [c_int, PI, PI, PI, PI, PD, PD, c_double, c_int, c_int], VP),
+                ("mgic_ref_tags_count", [VP, c_int], ctypes.c_long),
+                ("mgic_ref_tags_get", [VP, c_int, PI], None),
+                ("mgic_ref_tags_destroy", [VP], None),
+                ("mgic_ref_factory_create", [c_int, PI, PI, PI, PI, PI, c_double, c_double, c_double,
+                                             PI, PI, c_double, c_int, c_int, c_int], VP),
+                ("mgic_ref_factory_destroy", [VP], None),
+                ("mgic_ref_factory_average_type", [VP], c_int),
+                ("mgic_ref_factory_coef_set", [VP, c_int, c_int, c_int, PD], None),
+                ("mgic_ref_factory_coef_get", [VP, c_int, c_int, c_int, PD], None),
+                ("mgic_ref_factory_mg_new_op", [VP, c_int, c_int, PI], VP),
+                ("mgic_ref_factory_amr_new_op", [VP, PI, PI], VP),
+                ("mgic_ref_factory_ref_to_finer", [VP, PI, PI], c_int),
+                ("mgic_ref_op_info", [VP, PD, PI, PI, PI, PI, PI], None),
+                ("mgic_ref_op_box", [VP, c_int, PI], None),
+                ("mgic_ref_op_coef_get", [VP, c_int, c_int, PD], None),
+                ("mgic_ref_op_copier_count", [VP], c_int),
+                ("mgic_ref_op_copier_get", [VP, PI], None)):
             f = getattr(L, name)
             f.argtypes, f.restype = args, res
         for name in ("gsrbhelmholtzvc3d_", "vccomputeop3d_", "vccomputeres3d_", "restrictresvc3d_",
@@ -357,12 +397,22 @@ class Operator:
     which keeps them by reference, as the reference's factory does."""
 
     def __init__(self, boxes, domain, dx, alpha=1.0, beta=-1.0, periodic=(0, 0, 0),
-                 bc_lo=(0, 0, 0), bc_hi=(0, 0, 0), bc_value=0.0):
-        self.boxes = [tuple(int(v) for v in b) for b in boxes]
-        self.coarse_boxes = [tuple(v // 2 for v in b) for b in self.boxes]
+                 bc_lo=(0, 0, 0), bc_hi=(0, 0, 0), bc_value=0.0, _made=None):
         self._ghost = {}
         self._level = {}
         self._h = None
+        if _made is not None:  # an operator the reference's factory made (Factory below)
+            self._h = VP(_made)
+            nb = self.info()["nbox"]
+            out = (c_int * 6)()
+            self.boxes = []
+            for n in range(nb):
+                lib().mgic_ref_op_box(self._h, n, out)
+                self.boxes.append(tuple(out))
+            self.coarse_boxes = [tuple(v // 2 for v in b) for b in self.boxes]
+            return
+        self.boxes = [tuple(int(v) for v in b) for b in boxes]
+        self.coarse_boxes = [tuple(v // 2 for v in b) for b in self.boxes]
         h = lib().mgic_ref_op_create(len(self.boxes), _iarr([v for b in self.boxes for v in b]),
                                      _iarr(domain), _iarr(periodic), float(dx), float(alpha),
                                      float(beta), _iarr(bc_lo), _iarr(bc_hi), float(bc_value))
@@ -406,6 +456,31 @@ class Operator:
         x = self.boxes[b]
         out = np.empty(tuple(x[3 + d] - x[d] + 1 for d in (2, 1, 0)))
         return out if lib().mgic_ref_op_lambda_get(self._h, b, out.ctypes.data_as(PD)) else None
+
+    def info(self):
+        """dx, dxCrse, alpha, beta, refToCoarser, refToFiner, nbox, the ghost
+        layers of aCoef and bCoef, the domain box and its periodic flags."""
+        v, r, nb, g = (c_double * 4)(), (c_int * 2)(), c_int(), (c_int * 2)()
+        dom, per = (c_int * 6)(), (c_int * 3)()
+        lib().mgic_ref_op_info(self._h, v, r, byref(nb), g, dom, per)
+        return dict(dx=v[0], dxCrse=v[1], alpha=v[2], beta=v[3], refToCoarser=r[0], refToFiner=r[1],
+                    nbox=nb.value, coef_ghost=tuple(g), domain=tuple(dom), periodic=tuple(per))
+
+    def coef(self, which, b, full=True):
+        """m_aCoef (which 0) or m_bCoef (1) over box b, ghosts included (full)."""
+        g = self.info()["coef_ghost"][which]
+        x = self.boxes[b]
+        out = np.empty(tuple(x[3 + d] - x[d] + 1 + 2 * g for d in (2, 1, 0)))
+        lib().mgic_ref_op_coef_get(self._h, int(which), int(b), out.ctypes.data_as(PD))
+        return out if full or g == 0 else np.ascontiguousarray(out[g:-g, g:-g, g:-g])
+
+    def copier(self):
+        """The exchange copier's motions: (to box, cells lo+hi, from box, shift)."""
+        n = lib().mgic_ref_op_copier_count(self._h)
+        out = (c_int * (11 * max(n, 1)))()
+        lib().mgic_ref_op_copier_get(self._h, out)
+        return sorted((out[11 * m], tuple(out[11 * m + 1:11 * m + 7]), out[11 * m + 7],
+                       tuple(out[11 * m + 8:11 * m + 11])) for m in range(n))
 
     def residual(self, lhs, dpsi, rhs, homogeneous=False):
         lib().mgic_ref_op_residual(self._h, lhs, dpsi, rhs, int(bool(homogeneous)))
@@ -454,3 +529,151 @@ class Operator:
         if getattr(self, "_h", None):
             lib().mgic_ref_op_destroy(self._h)
             self._h = None
+
+
+# ---------------------------------------------------------------- factory, tagging, deck
+class MayDay(RuntimeError):
+    """The reference called MayDay::Error or MayDay::Abort; str() is its message."""
+
+
+UNWRITTEN_BITS = 0x7FF800006D676963
+"""What a LevelData the stand-in defines holds in every cell nobody wrote."""
+
+
+def unwritten(a) -> np.ndarray:
+    """Where an array still holds the stand-in's unwritten NaN."""
+    return np.ascontiguousarray(a).view(np.uint64) == np.uint64(UNWRITTEN_BITS)
+
+
+def _failed():
+    return MayDay(lib().mgic_ref_last_error().decode())
+
+
+class Factory:
+    """The reference's VariableCoeffPoissonOperatorFactory over AMR levels of
+    boxes: levels[l] a list of boxes, a[l][n] / b[l][n] the coefficients over
+    the valid cells of box n (ghosts stay unwritten).  by_deck False: define(),
+    then m_coefficient_average_type set to average_type when that is >= 0;
+    by_deck True: defineOperatorFactory with a PoissonParameters whose
+    coefficient_average_type is average_type."""
+
+    def __init__(self, levels, domain0, dx0, a, b, alpha=1.0, beta=-1.0, periodic=(0, 0, 0),
+                 bc_lo=(0, 0, 0), bc_hi=(0, 0, 0), bc_value=0.0, ref_ratio=None, coef_ghost=1,
+                 by_deck=False, average_type=-1):
+        self._h = None
+        self.levels = [[tuple(int(v) for v in x) for x in lev] for lev in levels]
+        nl = len(self.levels)
+        self.ref_ratio = list(ref_ratio) if ref_ratio is not None else [2] * nl
+        self.ghost = int(coef_ghost)
+        self.domains = [tuple(int(v) for v in domain0)]
+        for l in range(1, nl):
+            r, d = self.ref_ratio[l - 1], self.domains[-1]
+            self.domains.append(tuple(r * v for v in d[:3]) + tuple(r * (v + 1) - 1 for v in d[3:]))
+        h = lib().mgic_ref_factory_create(
+            nl, _iarr([len(x) for x in self.levels]), _iarr([v for lev in self.levels for x in lev for v in x]),
+            _iarr(domain0), _iarr(periodic), _iarr(self.ref_ratio), float(dx0), float(alpha), float(beta),
+            _iarr(bc_lo), _iarr(bc_hi), float(bc_value), self.ghost, int(bool(by_deck)), int(average_type))
+        if not h:
+            raise _failed()
+        self._h = VP(h)
+        for l in range(nl):
+            for n in range(len(self.levels[l])):
+                for which, src in ((0, a), (1, b)):
+                    whole = self.coef(l, which, n)
+                    g = self.ghost
+                    whole[(slice(g, -g),) * 3 if g else ...] = src[l][n]
+                    lib().mgic_ref_factory_coef_set(self._h, l, which, n, whole.ctypes.data_as(PD))
+
+    def coef(self, level, which, n):
+        """The factory's aCoef (0) or bCoef (1) of one box, ghosts included."""
+        x, g = self.levels[level][n], self.ghost
+        out = np.empty(tuple(x[3 + d] - x[d] + 1 + 2 * g for d in (2, 1, 0)))
+        lib().mgic_ref_factory_coef_get(self._h, level, which, n, out.ctypes.data_as(PD))
+        return out
+
+    @property
+    def average_type(self):
+        return lib().mgic_ref_factory_average_type(self._h)
+
+    def mg_new_op(self, level, depth):
+        """MGnewOp(the domain of `level`, depth): an Operator, or None for NULL."""
+        st = c_int()
+        h = lib().mgic_ref_factory_mg_new_op(self._h, int(level), int(depth), byref(st))
+        if st.value == 2:
+            raise _failed()
+        return None if st.value == 1 else Operator(None, None, 0.0, _made=h)
+
+    def amr_new_op(self, level=None, domain=None):
+        st = c_int()
+        h = lib().mgic_ref_factory_amr_new_op(self._h, _iarr(domain or self.domains[level]), byref(st))
+        if st.value:
+            raise _failed()
+        return Operator(None, None, 0.0, _made=h)
+
+    def ref_to_finer(self, level=None, domain=None):
+        r = c_int()
+        if lib().mgic_ref_factory_ref_to_finer(self._h, _iarr(domain or self.domains[level]), byref(r)):
+            raise _failed()
+        return r.value
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            lib().mgic_ref_factory_destroy(self._h)
+            self._h = None
+
+
+def tag_cells(levels, domains, values, dx, refine_thresh, tags_grow, periodic=(0, 0, 0), base_level=0):
+    """set_tag_cells: levels[l] a list of boxes, values[l][n] over box n,
+    domains[l] the level's domain box.  Returns, per level, an int array (n, 3)
+    of the tagged cells (i, j, k), ordered by k, then j, then i."""
+    nl = len(levels)
+    flat = np.concatenate([np.ascontiguousarray(v, dtype=np.float64).ravel()
+                           for lev in values for v in lev])
+    for lev, vals in zip(levels, values):
+        for x, v in zip(lev, vals):
+            assert np.shape(v) == tuple(x[3 + d] - x[d] + 1 for d in (2, 1, 0))
+    h = lib().mgic_ref_set_tag_cells(
+        nl, _iarr([len(x) for x in levels]), _iarr([v for lev in levels for x in lev for v in x]),
+        _iarr([v for d in domains for v in d]), _iarr(periodic), flat.ctypes.data_as(PD),
+        (c_double * nl)(*[float(x) for x in dx]), float(refine_thresh), int(tags_grow), int(base_level))
+    if not h:
+        raise _failed()
+    h = VP(h)
+    out = []
+    for l in range(nl):
+        n = lib().mgic_ref_tags_count(h, l)
+        cells = np.zeros((n, 3), dtype=np.int32)
+        if n:
+            lib().mgic_ref_tags_get(h, l, cells.ctypes.data_as(PI))
+        out.append(cells)
+    lib().mgic_ref_tags_destroy(h)
+    return out
+
+
+def domains_and_dx(nlevels, domain0, dx0, periodic=(0, 0, 0), ref_ratio=None):
+    """set_domains_and_dx: ([domain box per level], [periodic flags per level], [dx per level])."""
+    ref_ratio = list(ref_ratio) if ref_ratio is not None else [2] * nlevels
+    dom, per, dx = (c_int * (6 * nlevels))(), (c_int * (3 * nlevels))(), (c_double * nlevels)()
+    if lib().mgic_ref_set_domains_and_dx(nlevels, _iarr(domain0), _iarr(periodic), float(dx0),
+                                         _iarr(ref_ratio), dom, per, dx):
+        raise _failed()
+    return ([tuple(dom[6 * l:6 * l + 6]) for l in range(nlevels)],
+            [tuple(per[3 * l:3 * l + 3]) for l in range(nlevels)], list(dx))
+
+
+def poisson_parameters(deck: dict) -> dict:
+    """getPoissonParameters on a deck {name: [words]}: every field of the class."""
+    lib().mgic_ref_deck_clear()
+    for k, words in deck.items():
+        for w in words:
+            lib().mgic_ref_deck_add(k.encode(), str(w).encode())
+    p = _PoissonParameters()
+    if lib().mgic_ref_get_poisson_parameters(byref(p)):
+        raise _failed()
+    out = {}
+    for k, _ in _PoissonParameters._fields_:
+        v = getattr(p, k)
+        out[k] = v if isinstance(v, (int, float)) else list(v)
+    out["periodic"] = out["periodic"][:out.pop("n_periodic")]
+    out["refRatio"] = out["refRatio"][:out.pop("n_refRatio")]
+    return out

@@ -18,7 +18,7 @@ functions are pinned bit for bit to the compiled reference
   binary_bh64.json  params.txt's 64^3 SetBinaryBH aCoef / rhs at 64 sampled
                   cells (float.hex), psi = 1.
 
-The last two are written by the COMPILED reference (oracle/reference.py, which
+The last three are written by the COMPILED reference (oracle/reference.py, which
 needs a checkout of the reference and flang) and are skipped, with a notice,
 where that library is not built:
 
@@ -32,8 +32,14 @@ where that library is not built:
                   wrote for every case of tests/reference_operator_cases.py of
                   at most 16 cells a side, one array per box and field
                   written; the inputs are the ones the cases generate.
+  reference_factory.npz  what the reference's own operator factory,
+                  set_tag_cells and the operators the factory made gave for
+                  the tables of tests/reference_factory_cases.py: outputs
+                  only (per depth the scalars, coefficients, lambda, one
+                  residual and one relax(2); the projected tags).
 
-usage: python tests/golden/make_golden.py
+usage: python tests/golden/make_golden.py [name ...]
+       (no name: every fixture; else only the named ones, e.g. reference_factory)
 """
 import json
 import os
@@ -147,10 +153,21 @@ def reference_operator():
     assert reference.mayday_count() == 0
 
 
+def reference_factory():
+    from oracle import reference
+    from tests import reference_factory_cases
+    if not reference.build():
+        print("reference_factory.npz NOT regenerated: no reference checkout at",
+              reference.reference_dir(), "and no", reference.LIB)
+        return
+    reference.mayday_reset()
+    np.savez_compressed(reference_factory_cases.FIXTURE, **reference_factory_cases.build_fixture())
+    assert reference.mayday_count() == 0
+
+
 if __name__ == "__main__":
-    kernels12()
-    vcycle16()
-    binary_bh64()
-    reference_kernels()
-    reference_operator()
+    every = (kernels12, vcycle16, binary_bh64, reference_kernels, reference_operator, reference_factory)
+    for make in every:
+        if len(sys.argv) == 1 or make.__name__ in sys.argv[1:]:
+            make()
     print("fixtures written to", HERE)
