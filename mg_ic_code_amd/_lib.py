@@ -433,6 +433,47 @@ def ctt_call(name: str, *args) -> int:
     return st
 
 
+# ---- libmgic_zm.so (include/mgic_zm.h): the zero-mode kernel of a periodic
+# level, loaded on first use (momentum.py, zero_mode="project"); missing or
+# unloadable = an ImportError, no fallback
+ZM_LIB_PATH = os.path.join(_HERE, "libmgic_zm.so")
+ZM_SIGNATURES = {
+    "mgic_zm_last_error": [],
+    "mgic_zm_shift": [H, c_int, PH, PD],
+    "mgic_zm_launch_ledger_dump": [c_char_p],
+    "mgic_zm_launch_ledger_reset": [],
+}
+_zm = None
+
+
+def zm_lib() -> ctypes.CDLL:
+    global _zm
+    if _zm is None:
+        if not os.path.exists(ZM_LIB_PATH):
+            raise ImportError(f"{ZM_LIB_PATH} not found: build it with __graft_entry__.build()")
+        L = ctypes.CDLL(ZM_LIB_PATH)
+        for name, argtypes in ZM_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.argtypes = argtypes
+            fn.restype = c_char_p if name == "mgic_zm_last_error" else c_int
+        _zm = L
+    return _zm
+
+
+def zm_loaded() -> bool:
+    """Whether libmgic_zm.so has been loaded by this process."""
+    return _zm is not None
+
+
+def zm_call(name: str, *args) -> int:
+    L = zm_lib()
+    st = getattr(L, name)(*args)
+    if st < 0:
+        msg = L.mgic_zm_last_error()
+        raise MgicError(name, st, msg.decode() if msg else "")
+    return st
+
+
 def last_error() -> str:
     msg = lib.mgic_last_error()
     return msg.decode() if msg else ""

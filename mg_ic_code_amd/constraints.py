@@ -143,11 +143,21 @@ class ConstraintReport:
     l2_norm: per component of COMPONENTS, over the uncovered cells of every
     level; the L2 norm carries the cell volume (sqrt(sum x^2 dx_l^3)), as the
     NL loop's |dpsi|.  max_ham_abs: the max norm of Ham_abs, the scale
-    max_norm['Ham'] is judged by."""
+    max_norm['Ham'] is judged by.
+
+    momentum_net (a periodic solve with zero_mode="project"): the means m_i the
+    momentum solve removed from S_i.  What it then cannot solve for is
+    Mom_i = -m_i psi_0^-6 (plus truncation): max_norm_net and l2_norm_net are
+    the norms of Mom_i + m_i psi_0^-6, Mom_i with that predicted offset
+    subtracted, so "not solvable on a torus" can be told from "not solved".
+    All three are empty without it."""
     fields: List[ConstraintFields]
     max_norm: Dict[str, float] = field(default_factory=dict)
     l2_norm: Dict[str, float] = field(default_factory=dict)
     max_ham_abs: float = 0.0
+    momentum_net: List[float] = field(default_factory=list)
+    max_norm_net: Dict[str, float] = field(default_factory=dict)
+    l2_norm_net: Dict[str, float] = field(default_factory=dict)
 
     @property
     def relative_ham(self) -> float:
@@ -160,6 +170,10 @@ class ConstraintReport:
         out = [f"constraint {c}: max = {self.max_norm[c]:.16e} L2 = {self.l2_norm[c]:.16e}"
                for c in COMPONENTS]
         out.append(f"constraint max|Ham| / max Ham_abs = {self.relative_ham:.16e}")
+        for i, c in enumerate(COMPONENTS[1:]):
+            if c in self.max_norm_net:
+                out.append(f"constraint {c} + m psi_0^-6 (m = {self.momentum_net[i]:.16e}): "
+                           f"max = {self.max_norm_net[c]:.16e} L2 = {self.l2_norm_net[c]:.16e}")
         return out
 
 
@@ -170,7 +184,8 @@ def _field_norm(x: LevelData, ord: int) -> float:
 
 
 def constraints(psi, prm, phi0=None, punctures=None, matter=None,
-                constant_K: Optional[float] = None, momentum=None) -> ConstraintReport:
+                constant_K: Optional[float] = None, momentum=None,
+                momentum_net=None) -> ConstraintReport:
     """The constraints of the data at psi (a LevelData, or one per AMR level,
     coarsest first) and their norms.
 
@@ -183,7 +198,9 @@ def constraints(psi, prm, phi0=None, punctures=None, matter=None,
     own value, 0 for a PoissonParameters.  momentum: the
     momentum.MomentumFields of a solve with momentum=True (NLResult.momentum):
     the constraints of the total tensor Abar^BY_ij + LW_ij; None: of the
-    Bowen-York tensor alone.
+    Bowen-York tensor alone.  momentum_net: the three means a projected
+    periodic momentum solve removed from S_i (NLResult.momentum_net[-1]; one
+    level): the report also carries the norms of Mom_i + m_i psi_0^-6.
 
     On one level the norms are the operator's norm(x, 0) and norm(x, 2) *
     dx^1.5; over a hierarchy AMRSolver.computeNorm, so covered coarse cells
@@ -228,4 +245,20 @@ def constraints(psi, prm, phi0=None, punctures=None, matter=None,
     rep.max_norm = dict(zip(COMPONENTS, mx[:4]))
     rep.l2_norm = dict(zip(COMPONENTS, l2))
     rep.max_ham_abs = mx[4]
+    if momentum_net is not None:
+        if len(grids) != 1:
+            raise ValueError("momentum_net= needs one level")
+        from .output import grchombo_vars
+        grid, dx = grids[0], grids[0].dx
+        rep.momentum_net = [float(m) for m in momentum_net]
+        # psi_0^-6 = chi^1.5, chi the output's own component 0
+        w = [grchombo_vars(psis[0], n, bh, phi=phis[0] if phis is not None else None,
+                           punctures=punct, matter=mat)[0] ** 1.5 for n in range(grid.num_local)]
+        tmp = LevelData(grid)
+        tmp.set_zero()
+        for i, c in enumerate(COMPONENTS[1:]):
+            for n in range(grid.num_local):
+                tmp.upload(n, rep.fields[0].fields()[1 + i].download(n) + rep.momentum_net[i] * w[n])
+            rep.max_norm_net[c] = _field_norm(tmp, 0)
+            rep.l2_norm_net[c] = _field_norm(tmp, 2) * dx ** 1.5
     return rep

@@ -44,18 +44,37 @@ libmgic.so.
     fill_ghosts(...)               the ghost rule of W_i and LW_ij
     MomentumSolver                 the operators of the four solves, built once
 
-`poisson_solve(..., momentum=True)` runs them inside the NL loop; periodic
-bases are refused (the singular alpha = 0 problem needs sum S_i = 0, which a
-varying psi_0 does not give).
+`poisson_solve(..., momentum=True)` runs them inside the NL loop.
+
+Periodic bases.  -beta Lap on a torus is singular: constants are its null
+space and a right-hand side is in its range only when it sums to zero, which
+a varying psi_0 does not give S_i.  By default such a base is refused.  With
+zero_mode="project" (the deck's momentum_zero_mode = project) and one level,
+every one of the four solves is projected on both sides,
+
+    m = sum(rhs) / cells,  rhs <- rhs - m      (the system becomes consistent)
+    solve
+    x <- x - sum(x) / cells                    (the null-space component is fixed)
+
+with the sums the level's own dotProduct(f, ones), the mean formed on the
+host in double, and the subtraction k_zm_shift of libmgic_zm.so
+(include/mgic_zm.h), loaded on first use.  The removed means of S_i are the
+net momentum density the torus cannot carry; they are recorded
+(MomentumSolver.removed, NLResult.momentum_net).  The ghosts of every field
+across a periodic face come from the exchange; fillBC and the extrapolation
+have nothing to do there.  A periodic hierarchy is refused: the AMR operators
+do no refluxing, so the composite operator's columns do not sum to zero and a
+zero-sum right-hand side is not in its range.
 """
 from __future__ import annotations
 
 import ctypes
 from typing import List, Optional, Sequence
 
-from ._lib import call, ctt_call
+from ._lib import call, ctt_call, zm_call
 from .core import (AMRMultiGrid, AMRSolver, BH_KEYS, BiCGStabSolver, Grid, LevelData,
                    MultilevelLinearOp, OperatorParams, SolverParams, defineOperatorFactory)
+from .params import ZERO_MODES
 from .matter import FilledMatter, MatterArgumentError, ScalarPotential, _pot, table_or_null
 
 # the order of the six stored components, as the A_ij of the output
@@ -99,19 +118,37 @@ class MomentumFields:
         return self.LW[level]
 
 
-def check_momentum_request(mat, periodic: bool, func: str = "poisson_solve") -> None:
+def resolve_zero_mode(zero_mode: Optional[str], prm) -> str:
+    """poisson_solve's zero_mode: None -- the deck's momentum_zero_mode (absent:
+    "refuse"); anything but the two accepted values is a ValueError."""
+    if zero_mode is None:
+        zero_mode = getattr(prm, "momentum_zero_mode", "refuse")
+    if zero_mode not in ZERO_MODES:
+        raise ValueError(f"zero_mode must be 'refuse' or 'project', got {zero_mode!r}")
+    return zero_mode
+
+
+def check_momentum_request(mat, periodic: bool, func: str = "poisson_solve",
+                           zero_mode: str = "refuse", num_levels: int = 1) -> None:
     """The refusals of momentum=True, raised before anything is launched:
-    no matter, a matter without a Pi_0, a periodic base."""
+    no matter, a matter without a Pi_0, a periodic base without
+    zero_mode="project", a periodic hierarchy with it."""
     if mat is None:
         raise MatterArgumentError(func, "momentum=True needs matter: the source of the momentum "
                                   "constraint is the scalar field's Pi d_i phi")
     if getattr(mat, "pi", None) is None:
         raise MatterArgumentError(func, "momentum=True needs a matter with a Pi_0: with Pi = 0 "
                                   "the momentum constraint has no source to solve for")
-    if periodic:
+    if periodic and zero_mode != "project":
         raise ValueError("momentum=True on a periodic base is not supported: the singular "
                          "alpha = 0 problem Lap V_i = S_i needs sum S_i = 0 over the domain, "
-                         "which a varying psi_0 does not give")
+                         "which a varying psi_0 does not give; zero_mode='project' (the deck's "
+                         "momentum_zero_mode = project) removes the mean of S_i and reports it")
+    if periodic and num_levels > 1:
+        raise ValueError("zero_mode='project' on a periodic hierarchy is not supported: the AMR "
+                         "operators do no refluxing, so the composite operator's columns do not "
+                         "sum to zero and a zero-sum right-hand side is not in its range; use "
+                         "one level")
 
 
 def momentum_source(psi: LevelData, out: Sequence[LevelData], bh: dict,
@@ -161,6 +198,28 @@ def ctt_launch_ledger() -> dict:
         os.unlink(path)
 
 
+def shift(comm, fields: Sequence[LevelData], consts: Sequence[float]) -> None:
+    """fields[i] -= consts[i] on the valid cells of every local box, one or
+    three fields in one pass (k_zm_shift<1>, <3>); no ghost cell is written."""
+    zm_call("mgic_zm_shift", comm.handle, len(fields), handles(fields),
+            (ctypes.c_double * len(fields))(*[float(c) for c in consts]))
+
+
+def zm_launch_ledger() -> dict:
+    """{kernel: launches so far in this process} of libmgic_zm.so."""
+    import os
+    import tempfile
+
+    from .core import read_launch_ledger
+    fd, path = tempfile.mkstemp(prefix="mgic_zm_ledger_")
+    os.close(fd)
+    try:
+        zm_call("mgic_zm_launch_ledger_dump", path.encode())
+        return read_launch_ledger(path)
+    finally:
+        os.unlink(path)
+
+
 def fill_ghosts(fields, amr: Optional[AMRSolver] = None) -> None:
     """Ghost layer 1 of W_i or LW_ij.  fields[l]: the LevelData of level l with
     that component (coarsest first; one level: a list of one).  Per level:
@@ -177,11 +236,27 @@ def fill_ghosts(fields, amr: Optional[AMRSolver] = None) -> None:
 class MomentumSolver:
     """The operators of the four solves: -beta Lap with the deck's boundary
     conditions (aCoef = 0, bCoef = 1), the NL loop's multigrid and BiCGStab
-    settings.  Nothing in them depends on psi, so they are built once."""
+    settings.  Nothing in them depends on psi, so they are built once.
+    zero_mode "project" on a periodic one-level base: every solve is projected
+    (the module's docstring), and `removed` keeps the mean taken out of each
+    right-hand side, in the order of the solves, until the caller clears it.
+    On a base that is not periodic zero_mode changes nothing."""
 
-    def __init__(self, grids: Sequence[Grid], prm, op_params: OperatorParams, sp: SolverParams):
+    def __init__(self, grids: Sequence[Grid], prm, op_params: OperatorParams, sp: SolverParams,
+                 zero_mode: str = "refuse"):
         self.grids = list(grids)
         self.prm = prm
+        self.project = zero_mode == "project" and all(self.grids[0].periodic)
+        if self.project and len(self.grids) > 1:
+            raise ValueError("zero_mode='project' needs a one-level base")
+        self.removed: List[float] = []
+        self.source_max: List[float] = []
+        self.ones = None
+        if self.project:
+            d = self.grids[0].domain
+            self.cells = (d[3] - d[0] + 1) * (d[4] - d[1] + 1) * (d[5] - d[2] + 1)
+            self.ones = LevelData(self.grids[0])
+            self.ones.set_val(1.0)
         self.rhs_scale = -float(op_params.beta)
         self.a = [LevelData(g) for g in self.grids]
         self.b = [LevelData(g) for g in self.grids]
@@ -207,12 +282,20 @@ class MomentumSolver:
             return self.ops[0].norm(rhs[0], 0)
         return self.amr.norm(rhs, 0)
 
-    def solve(self, x: List[LevelData], rhs: List[LevelData]) -> int:
-        """Lap x = rhs over the hierarchy (x, rhs: one LevelData per level; rhs
-        is scaled by -beta in place), x the initial guess; then x's ghost layer
-        is filled as dpsi's is (coarse-fine interpolation, exchange, the
-        homogeneous boundary condition).  Returns the BiCGStab iterations; a
-        right-hand side of zeros has the solution zero and takes none."""
+    def mean(self, f: LevelData) -> float:
+        """sum(f) / cells over the periodic level: the level's dotProduct(f,
+        ones) (reduced over the ranks), divided on the host."""
+        return self.ops[0].dotProduct(f, self.ones) / self.cells
+
+    def remove_means(self, fields: Sequence[LevelData]) -> List[float]:
+        """Subtract its mean from each of one or three fields of the level
+        (one pass of k_zm_shift); returns the means removed."""
+        means = [self.mean(f) for f in fields]
+        shift(self.grids[0].comm, fields, means)
+        return means
+
+    def _solve(self, x: List[LevelData], rhs: List[LevelData]) -> int:
+        """The all-zero shortcut, the scaling by -beta and the solve."""
         if self._max_norm(rhs) == 0.0:
             for f in x:
                 f.set_zero()
@@ -221,14 +304,48 @@ class MomentumSolver:
             for l, f in enumerate(rhs):
                 self.ops[l].scale(f, self.rhs_scale)
         if self.amr is None:
-            its = self.solver.solve(x[0], rhs[0])
-        else:
-            its = self.solver.solve(x, rhs)
+            return self.solver.solve(x[0], rhs[0])
+        return self.solver.solve(x, rhs)
+
+    def _fill(self, x: List[LevelData]) -> None:
         for l, f in enumerate(x):
             if l > 0:
                 self.amr.cf_interp(l, f, x[l - 1])
             f.exchange()
             self.ops[l].fillBC(f, True)
+
+    def solve(self, x: List[LevelData], rhs: List[LevelData]) -> int:
+        """Lap x = rhs over the hierarchy (x, rhs: one LevelData per level; rhs
+        is scaled by -beta in place), x the initial guess; then x's ghost layer
+        is filled as dpsi's is (coarse-fine interpolation, exchange, the
+        homogeneous boundary condition).  Returns the BiCGStab iterations; a
+        right-hand side of zeros has the solution zero and takes none.  With
+        the projection on, the mean of rhs is removed first (and appended to
+        `removed`), and the mean of x after the solve, before its ghosts are
+        filled.  The shortcut is looked for after the projection: a field of
+        zeros has the mean 0.0, stays as it is and takes it as before, and a
+        constant one, which has no solution part either, takes it too."""
+        if self.project:
+            self.removed.extend(self.remove_means(rhs))
+        its = self._solve(x, rhs)
+        if self.project:
+            self.remove_means(x)
+        self._fill(x)
+        return its
+
+    def solve_three(self, xs: Sequence[List[LevelData]],
+                    rhss: Sequence[List[LevelData]]) -> List[int]:
+        """solve for three components.  With the projection on, the three
+        right-hand sides lose their means in one pass and the three solutions
+        in another (k_zm_shift<3>); `source_max` keeps max|rhs_i| as they came."""
+        if not self.project:
+            return [self.solve(x, r) for x, r in zip(xs, rhss)]
+        self.source_max = [self.ops[0].norm(r[0], 0) for r in rhss]
+        self.removed.extend(self.remove_means([r[0] for r in rhss]))
+        its = [self._solve(x, r) for x, r in zip(xs, rhss)]
+        self.remove_means([x[0] for x in xs])
+        for x in xs:
+            self._fill(x)
         return its
 
 
@@ -244,10 +361,8 @@ def solve_vector_potential(ms: MomentumSolver, mf: MomentumFields, psi: Sequence
     for l in range(nlev):
         momentum_source(psi[l], ms.rhs[l], bh, mat.potential, mat.level(l), punctures,
                         phi[l] if phi is not None else None)
-    its = []
-    for i in range(3):
-        its.append(ms.solve([mf.V[l][i] for l in range(nlev)],
-                            [ms.rhs[l][i] for l in range(nlev)]))
+    its = ms.solve_three([[mf.V[l][i] for l in range(nlev)] for i in range(3)],
+                         [[ms.rhs[l][i] for l in range(nlev)] for i in range(3)])
     for l in range(nlev):
         div_rhs(comm, mf.V[l], ms.rhs[l][0])
     its.append(ms.solve(mf.U, [ms.rhs[l][0] for l in range(nlev)]))

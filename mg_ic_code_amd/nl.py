@@ -14,7 +14,9 @@ max_level = 0:
 
 On a periodic domain each NL iteration first sets K from the integrability
 condition: K = -sqrt(|sum(integrand) dV| / volume), with the integrand of
-set_constant_K_integrand (:133-147).  Every field stays in HBM, and each step
+set_constant_K_integrand (:133-147); with the momentum solve on such a
+domain (zero_mode="project", momentum.py) its step comes first and the
+integrand is the total tensor's.  Every field stays in HBM, and each step
 is a libmgic kernel.  With output_dir set, the reference's HDF5 files are
 written as it writes them: output_solver_data before every solve (:181) and
 output_final_data after the loop (:229), through libmgic_io (output.py).
@@ -48,8 +50,9 @@ from ._lib import call
 from .constraints import constraints as constraint_report
 from .output import output_final_data, output_solver_data
 from .matter import fill_matter, resolve_matter, set_nl_coefs_matter, set_nl_integrand_matter
-from .momentum import (MomentumFields, MomentumSolver, check_momentum_request, set_longitudinal,
-                       set_nl_coefs_ctt, solve_vector_potential)
+from .momentum import (MomentumFields, MomentumSolver, check_momentum_request, resolve_zero_mode,
+                       set_longitudinal, set_nl_coefs_ctt, set_nl_integrand_ctt,
+                       solve_vector_potential)
 from .params import PoissonParameters
 from .phi import resolve_phi0, set_nl_coefs_phi, set_nl_integrand_phi
 from .punctures import resolve_punctures, set_nl_coefs_punct, set_nl_integrand_punct
@@ -83,6 +86,11 @@ class NLResult:
     # four solves (V_x, V_y, V_z, U)
     momentum: object = None
     momentum_iterations: List[List[int]] = field(default_factory=list)
+    # zero_mode="project" on a periodic base: per NL iteration the three means
+    # removed from S_i (the net momentum density the torus cannot carry, before
+    # the -beta scaling), and each divided by that iteration's max|S_i|
+    momentum_net: List[List[float]] = field(default_factory=list)
+    momentum_net_relative: List[List[float]] = field(default_factory=list)
 
 
 def set_nl_integrand(psi: LevelData, out: LevelData, bh: dict) -> None:
@@ -109,8 +117,10 @@ def _coefs(psi, phi, a, rhs, bh, punct=None, mat=None, lev=0, mom=None) -> None:
         set_nl_coefs_phi(psi, phi, a, rhs, bh)
 
 
-def _integrand(psi, phi, out, bh, punct=None, mat=None, lev=0) -> None:
-    if mat is not None:
+def _integrand(psi, phi, out, bh, punct=None, mat=None, lev=0, mom=None) -> None:
+    if mom is not None:
+        set_nl_integrand_ctt(psi, out, bh, mat.potential, mom.lw(lev), mat.level(lev), punct, phi)
+    elif mat is not None:
         set_nl_integrand_matter(psi, out, bh, mat.potential, mat.level(lev), punct, phi)
     elif punct is not None:
         set_nl_integrand_punct(psi, out, bh, punct, phi=phi)
@@ -125,7 +135,8 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
                   max_NL_iterations: Optional[int] = None,
                   output_dir: Optional[str] = None, phi0=None, punctures=None,
                   matter=None, constraints: bool = False,
-                  momentum: Optional[bool] = None) -> NLResult:
+                  momentum: Optional[bool] = None,
+                  zero_mode: Optional[str] = None) -> NLResult:
     """phi0: None -- the analytic Gaussian, evaluated in the kernels; else a
     phi.PhiProfile, or one pre-filled LevelData per level: phi_0 is stored once
     before the NL loop (set_initial_conditions, SetLevelData.cpp:32-71) and the
@@ -148,13 +159,24 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
     Abar^BY_ij + LW_ij; the fields are attached as NLResult.momentum, and the
     constraint report and the final data carry the total tensor.  It needs a
     matter with a Pi_0 (MatterArgumentError otherwise) and a base that is not
-    periodic (ValueError).  None: the deck's solve_momentum; False: nothing
-    of it is loaded or launched."""
+    periodic (ValueError) unless zero_mode says otherwise.  None: the deck's
+    solve_momentum; False: nothing of it is loaded or launched.
+    zero_mode: "refuse" -- momentum=True on a periodic base is a ValueError;
+    "project" -- on a periodic one-level base the momentum solve removes the
+    mean of each of its four right-hand sides and solutions (momentum.py), the
+    means removed from S_i are NLResult.momentum_net, and each NL iteration
+    runs the momentum step first so that K comes from the total tensor; a
+    periodic hierarchy is refused (ValueError), and on a base that is not
+    periodic it changes nothing.  None: the deck's momentum_zero_mode; any
+    other value is a ValueError."""
     punct = resolve_punctures(punctures, prm)
+    zero_mode = resolve_zero_mode(zero_mode, prm)
     if momentum is None:
         momentum = bool(getattr(prm, "solve_momentum", 0))
     if momentum:  # refused before anything is stored or launched
-        check_momentum_request(resolve_matter(matter, prm), bool(prm.is_periodic))
+        nlev = len(grid) if isinstance(grid, (list, tuple)) else 1
+        check_momentum_request(resolve_matter(matter, prm), bool(prm.is_periodic),
+                               zero_mode=zero_mode, num_levels=nlev)
     if isinstance(grid, (list, tuple)):
         if len(grid) > 1:
             return _poisson_solve_amr(list(grid), prm, max_depth, prolong_type, bottom_solver,
@@ -186,26 +208,30 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
         msolve = MomentumSolver([grid], prm, op_params, SolverParams(
             max_depth=depth, n_pre=prm.numMGsmooth, n_post=prm.numMGsmooth,
             n_bottom=prm.numMGsmooth, bottom_solver=bottom_solver,
-            agglomerate_below=32 if grid.comm.size > 1 else 0))
+            agglomerate_below=32 if grid.comm.size > 1 else 0), zero_mode)
     n_nl = prm.max_NL_iterations if max_NL_iterations is None else max_NL_iterations
     dx = grid.dx
     ones = integrand = None
     volume = prm.domainLength[0] * prm.domainLength[1] * prm.domainLength[2]
     for it in range(n_nl):
+        if momentum and periodic:
+            # the momentum step first, so that K below comes from the total
+            # tensor.  S_i does not depend on K: mgic_field_momentum_source
+            # (bh_constraints with `source`) reads constant_K for Ham alone,
+            # which it does not write, so the order leaves S_i as it was
+            _momentum_step(res, msolve, mom, psi, bh, mat, punct, phis)
         if periodic:  # integrability condition for K (:133-147)
             if integrand is None:
                 integrand, ones = LevelData(grid), LevelData(grid)
                 ones.set_val(1.0)
             bh["constant_K"] = 0.0
-            _integrand(psi, phi, integrand, bh, punct, mat)
+            _integrand(psi, phi, integrand, bh, punct, mat, 0, mom)
             tmp_op = defineOperatorFactory(grid, a, b, op_params).AMRnewOp()
             integral = tmp_op.dotProduct(integrand, ones) * dx ** 3  # computeSum
             bh["constant_K"] = -math.sqrt(abs(integral) / volume)
             res.constant_K.append(bh["constant_K"])
-        if momentum:  # V_i and U at the current psi, then LW_ij of the total tensor
-            res.momentum_iterations.append(
-                solve_vector_potential(msolve, mom, [psi], bh, mat, punct, phis))
-            set_longitudinal(msolve, mom)
+        if momentum and not periodic:
+            _momentum_step(res, msolve, mom, psi, bh, mat, punct, phis)
         _coefs(psi, phi, a, rhs, bh, punct, mat, 0, mom)  # :155-161
         fac = defineOperatorFactory(grid, a, b, op_params)
         # N > 1: depths whose boxes are below 32 cells a side are gathered to
@@ -238,8 +264,24 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
                               punctures=punct, matter=mat, constraints=constraints, momentum=mom)
     finish_nl_loop(res, write)
     if constraints:
-        res.constraints = constraint_report(psi, bh, phis, punct, mat, momentum=mom)
+        res.constraints = constraint_report(
+            psi, bh, phis, punct, mat, momentum=mom,
+            momentum_net=res.momentum_net[-1] if res.momentum_net else None)
     return res
+
+
+def _momentum_step(res: NLResult, msolve, mom, psi, bh, mat, punct, phis) -> None:
+    """V_i and U at the current psi, then LW_ij of the total tensor; with the
+    zero mode projected, the means removed from S_i."""
+    res.momentum_iterations.append(
+        solve_vector_potential(msolve, mom, [psi], bh, mat, punct, phis))
+    set_longitudinal(msolve, mom)
+    if msolve.project:
+        net = msolve.removed[:3]
+        msolve.removed.clear()
+        res.momentum_net.append(net)
+        res.momentum_net_relative.append([m / s if s != 0.0 else 0.0
+                                          for m, s in zip(net, msolve.source_max)])
 
 
 def _op_params(prm: PoissonParameters, prolong_type: int) -> OperatorParams:

@@ -24,6 +24,10 @@ def parse_parmparse(text: str) -> Dict[str, List[str]]:
     return out
 
 
+# the values of momentum_zero_mode (poisson_solve's zero_mode)
+ZERO_MODES = ("refuse", "project")
+
+
 @dataclass
 class PoissonParameters:
     alpha: float = 1.0
@@ -71,6 +75,12 @@ class PoissonParameters:
     # solve_momentum = 0|1 (not a key of the reference): 1 solves the momentum
     # constraint for the matter's Pi d_i phi source (momentum.py); absent: 0
     solve_momentum: int = 0
+    # momentum_zero_mode = refuse|project (not a key of the reference): what the
+    # momentum solve does on a periodic base, where its operator is singular;
+    # project removes the mean of every right-hand side and solution
+    # (momentum.py); absent: refuse.  It has no effect on a base that is not
+    # periodic
+    momentum_zero_mode: str = "refuse"
 
     # what getPoissonParameters derives besides (PoissonParameters.cpp:68, :78-79,
     # :111-128): one more level than max_level, ratio 2 on every level, the
@@ -187,6 +197,11 @@ def read_params(text: str, overrides: Optional[Dict[str, str]] = None) -> Poisso
         if sm not in (0, 1):
             raise ValueError(f"solve_momentum must be 0 or 1, got {sm}")
         p.solve_momentum = sm
+    zm = get("momentum_zero_mode", str, required=False)
+    if zm is not None:
+        if zm not in ZERO_MODES:
+            raise ValueError(f"momentum_zero_mode must be refuse or project, got {zm!r}")
+        p.momentum_zero_mode = zm
     return p
 
 

@@ -30,13 +30,19 @@ max|Ham| / max Ham_abs.
 
 With --momentum (or the deck's solve_momentum = 1) the momentum constraint is
 solved for the matter's Pi d_i phi source (mg_ic_code_amd/momentum.py): needs
-a matter with a Pi, and a base that is not periodic.
+a matter with a Pi, and a base that is not periodic -- unless
+--momentum-zero-mode project (or the deck's momentum_zero_mode = project) is
+given: on a periodic one-level base the mean of every right-hand side and
+solution of the momentum solve is then removed, and the means removed from
+S_i (the net momentum density the torus cannot carry) are printed per
+iteration and put in the JSON summary.
 
 usage: python tools/run_poisson.py [params.txt] [--size N] [--boxes-per-rank x,y,z]
                                    [--max-level K] [--phi gaussian|sine]
                                    [--puncture "m x y z Px Py Pz Jx Jy Jz"]...
                                    [--potential "V0 mass lambda"] [--pi VALUE]
                                    [--constraints] [--momentum]
+                                   [--momentum-zero-mode refuse|project]
 """
 import argparse
 import json
@@ -69,6 +75,9 @@ def main():
                     help="report the constraint norms of the solved data")
     ap.add_argument("--momentum", action="store_true",
                     help="solve the momentum constraint for the matter's Pi d_i phi source")
+    ap.add_argument("--momentum-zero-mode", choices=("refuse", "project"), default=None,
+                    help="the momentum solve on a periodic base: refuse it, or project the zero "
+                         "mode out (default: the deck's momentum_zero_mode)")
     args = ap.parse_args()
     import mg_ic_code_amd as mg
     from mg_ic_code_amd.decomposition import decompose
@@ -113,14 +122,18 @@ def main():
     t0 = time.perf_counter()
     res = poisson_solve(levels, prm, max_depth=args.max_depth, phi0=phi0, punctures=punct,
                         matter=matter, constraints=args.constraints,
-                        momentum=True if args.momentum else None)
+                        momentum=True if args.momentum else None,
+                        zero_mode=args.momentum_zero_mode)
     mg.device_synchronize()
     dt = time.perf_counter() - t0
     for i, (nrm, it) in enumerate(zip(res.dpsi_norms, res.linear_iterations)):
         print(f"Main Loop Iteration {i + 1}: {it} BiCGStab iterations, norm of dpsi {nrm:.6e}")
     for i, its in enumerate(res.momentum_iterations):
         print(f"Main Loop Iteration {i + 1}: momentum solves V1 V2 V3 U: "
-              + " ".join(str(v) for v in its) + " BiCGStab iterations")
+              + " ".join(str(v) for v in its) + " BiCGStab iterations"
+              + ("; removed means of S1 S2 S3: "
+                 + " ".join(f"{m:.16e}" for m in res.momentum_net[i])
+                 if res.momentum_net else ""))
     if args.constraints:
         for line in res.constraints.lines():
             print(line)
@@ -137,6 +150,9 @@ def main():
         out["constant_K"] = res.constant_K
     if res.momentum is not None:
         out["momentum_iterations"] = res.momentum_iterations
+    if res.momentum_net:
+        out["momentum_net"] = res.momentum_net
+        out["momentum_net_relative"] = res.momentum_net_relative
     print(json.dumps(out))
 
 
