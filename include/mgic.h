@@ -388,7 +388,8 @@ MGIC_API int mgic_mixed_fmg(mgic_mixed m, mgic_field phi, mgic_field rhs, mgic_f
 
 /* ---- AMR levels > 0 ([Chombo] AMRPoissonOp multi-level
  * operators restated: QuadCFInterp, AMROperator / AMRResidual (reflux a
- * no-op as in the reference), AMRRestrict, AMRProlong, AMRUpdateResidual,
+ * no-op as in the reference unless switched on, mgic_amr_set_reflux below),
+ * AMRRestrict, AMRProlong, AMRUpdateResidual,
  * AMRMultiGrid's multi-level V-cycle).  grids[0] tiles its domain; level
  * l+1's domain is level l's refined by 2 and its boxes are properly nested
  * (mgic_grid_create_patches).  Level 0 is solved by its MultiGrid (base). */
@@ -429,6 +430,10 @@ MGIC_API int mgic_amr_residual_field(mgic_amr a, int level, mgic_field *out); /*
  * dotProduct / norm count each physical cell once, on its finest level) */
 MGIC_API int mgic_amr_apply_op(mgic_amr a, const mgic_field *lhs, const mgic_field *x,
                                int homogeneous);
+/* r = rhs - L(phi) with the same operator (the residual mgic_amr_solve takes),
+ * covered coarse cells zeroed */
+MGIC_API int mgic_amr_composite_residual(mgic_amr a, const mgic_field *r, const mgic_field *phi,
+                                         const mgic_field *rhs, int homogeneous);
 MGIC_API int mgic_amr_dot(mgic_amr a, const mgic_field *x, const mgic_field *y, double *out);
 MGIC_API int mgic_amr_norm(mgic_amr a, const mgic_field *x, int ord, double *out);
 /* computeNorm / computeSum (Main_PoissonSolver.cpp:144-145,208-209): covered
@@ -438,6 +443,62 @@ MGIC_API int mgic_amr_composite_sum(mgic_amr a, const mgic_field *x, double *out
 /* MultilevelLinearOp::preCond: e = 0, `iters` AMR V-cycle iterations on
  * (e, r) with homogeneous physical BCs */
 MGIC_API int mgic_amr_precondition(mgic_amr a, const mgic_field *e, const mgic_field *r, int iters);
+
+/* ---- reflux at coarse-fine faces (include/mgic_reflux.h has
+ * the term).  Off by default: the composite operator is then the reference's,
+ * not conservative.  On: mgic_amr_apply_op, mgic_amr_init_residual /
+ * _iteration, _precondition and _solve add the term to every level that has
+ * a finer one, and the V-cycle's downsweep adds the fine correction's to the
+ * restricted residual.  mgic_amr_operator / _residual (one level) never do.
+ * With the switch on, _apply_op, _init_residual and _solve's residuals first
+ * overwrite the covered cells of their input (x, phi) with the average of the
+ * finer level, so the result depends on the uncovered cells alone, bit for
+ * bit; _iteration and _precondition leave that average there anyway.
+ * The kernel is libmgic_reflux.so's, reached through this table: one entry of
+ * `cells` per uncovered cell with a covered face neighbour (sorted by box and
+ * offset), its faces (bits of `mask`: x-lo ... z-hi) consecutive in `faces`
+ * from `first`. */
+typedef struct mgic_reflux_cell {
+  long long off;  /* the cell, from its box's valid-lo */
+  int box;        /* local box of the coarse level */
+  int first;      /* its first entry of the face table */
+  int mask;       /* its interface faces, bit 0 x-lo ... bit 5 z-hi */
+  int pad;
+} mgic_reflux_cell;
+typedef struct mgic_reflux_face {
+  long long foff;   /* fine in-cell (0, 0) behind the face, from its box's valid-lo */
+  long long cstep;  /* coarse cell -> its covered neighbour */
+  long long fstep;  /* fine in-cell -> the ghost across the face */
+  long long ft0;    /* fine stride of the lower tangential direction */
+  long long ft1;    /* ... of the higher one */
+  int fbox;         /* local box of the fine level */
+  int pad;
+} mgic_reflux_face;
+typedef struct mgic_reflux_table {
+  int version; /* 1 */
+  /* target[c] = target[c] +/- (coef * b[c]) * sum of c's terms for the
+   * ncell cells (device tables; phi_c may be NULL: a zero coarse field);
+   * sign > 0 adds; 0, or a negative status with last_error() set */
+  int (*apply)(const mgic_reflux_cell *cells, const mgic_reflux_face *faces, long long ncell,
+               double *const *target, double *const *phi_c, double *const *phi_f,
+               double *const *b, double coef, double dx_c, double dx_f, int sign, void *stream);
+  const char *(*last_error)(void);
+} mgic_reflux_table;
+/* the launcher (libmgic_reflux.so's mgic_reflux_register calls this); the
+ * table must outlive every mgic_amr */
+MGIC_API int mgic_amr_reflux_register(const mgic_reflux_table *t);
+/* on != 0 builds the tables (MGIC_ESTATE without a registered launcher,
+ * MGIC_EBADARG when a box of a refined level or its refinement is not
+ * local); with one level it changes nothing and needs no launcher */
+MGIC_API int mgic_amr_set_reflux(mgic_amr a, int on);
+/* the per-level primitive, whatever the switch: level has a finer level;
+ * target and phi_coarse live on it, phi_fine on level + 1 with its ghosts as
+ * mgic_amr_operator(level + 1) leaves them, phi_coarse's face ghosts as
+ * mgic_amr_operator(level) does.  phi_coarse == NULL: a zero coarse field.
+ * sign > 0: target += term (an operator); sign < 0: target -= term (a
+ * residual) */
+MGIC_API int mgic_amr_reflux(mgic_amr a, int level, mgic_field target, mgic_field phi_coarse,
+                             mgic_field phi_fine, int sign);
 
 /* ---- output (WriteOutput.H).  For local box n, planes
  * [k0, k0+nk) of its valid box: the components the reference writes,

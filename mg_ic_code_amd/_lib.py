@@ -203,11 +203,15 @@ SIGNATURES = {
     "mgic_amr_iteration": [H, POINTER(H), POINTER(H), c_int, PD],
     "mgic_amr_residual_field": [H, c_int, PH],
     "mgic_amr_apply_op": [H, POINTER(H), POINTER(H), c_int],
+    "mgic_amr_composite_residual": [H, POINTER(H), POINTER(H), POINTER(H), c_int],
     "mgic_amr_dot": [H, POINTER(H), POINTER(H), PD],
     "mgic_amr_norm": [H, POINTER(H), c_int, PD],
     "mgic_amr_composite_norm": [H, POINTER(H), c_int, PD],
     "mgic_amr_composite_sum": [H, POINTER(H), PD],
     "mgic_amr_precondition": [H, POINTER(H), POINTER(H), c_int],
+    "mgic_amr_reflux_register": [c_void_p],
+    "mgic_amr_set_reflux": [H, c_int],
+    "mgic_amr_reflux": [H, c_int, H, H, H, c_int],
     "mgic_mixed_create": [H, POINTER(MGParams), PH],
     "mgic_mixed_destroy": [H],
     "mgic_mixed_num_depths": [H, PI],
@@ -470,6 +474,53 @@ def zm_call(name: str, *args) -> int:
     st = getattr(L, name)(*args)
     if st < 0:
         msg = L.mgic_zm_last_error()
+        raise MgicError(name, st, msg.decode() if msg else "")
+    return st
+
+
+# ---- libmgic_reflux.so (include/mgic_reflux.h): the reflux kernel of the
+# coarse-fine faces, loaded on first use (AMRSolver(..., reflux=True) with more
+# than one level, AMRSolver.reflux) and registered with libmgic then; missing
+# or unloadable = an ImportError, no fallback
+REFLUX_LIB_PATH = os.path.join(_HERE, "libmgic_reflux.so")
+REFLUX_SIGNATURES = {
+    "mgic_reflux_last_error": [],
+    "mgic_reflux_register": [],
+    "mgic_reflux_launch_ledger_dump": [c_char_p],
+    "mgic_reflux_launch_ledger_reset": [],
+}
+_reflux = None
+
+
+def reflux_lib() -> ctypes.CDLL:
+    global _reflux
+    if _reflux is None:
+        if not os.path.exists(REFLUX_LIB_PATH):
+            raise ImportError(
+                f"{REFLUX_LIB_PATH} not found: build it with __graft_entry__.build()")
+        L = ctypes.CDLL(REFLUX_LIB_PATH)
+        for name, argtypes in REFLUX_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.argtypes = argtypes
+            fn.restype = c_char_p if name == "mgic_reflux_last_error" else c_int
+        st = L.mgic_reflux_register()
+        if st < 0:
+            msg = L.mgic_reflux_last_error()
+            raise MgicError("mgic_reflux_register", st, msg.decode() if msg else "")
+        _reflux = L
+    return _reflux
+
+
+def reflux_loaded() -> bool:
+    """Whether libmgic_reflux.so has been loaded by this process."""
+    return _reflux is not None
+
+
+def reflux_call(name: str, *args) -> int:
+    L = reflux_lib()
+    st = getattr(L, name)(*args)
+    if st < 0:
+        msg = L.mgic_reflux_last_error()
         raise MgicError(name, st, msg.decode() if msg else "")
     return st
 

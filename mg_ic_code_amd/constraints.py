@@ -185,7 +185,7 @@ def _field_norm(x: LevelData, ord: int) -> float:
 
 def constraints(psi, prm, phi0=None, punctures=None, matter=None,
                 constant_K: Optional[float] = None, momentum=None,
-                momentum_net=None) -> ConstraintReport:
+                momentum_net=None, reflux: bool = False) -> ConstraintReport:
     """The constraints of the data at psi (a LevelData, or one per AMR level,
     coarsest first) and their norms.
 
@@ -199,8 +199,11 @@ def constraints(psi, prm, phi0=None, punctures=None, matter=None,
     momentum.MomentumFields of a solve with momentum=True (NLResult.momentum):
     the constraints of the total tensor Abar^BY_ij + LW_ij; None: of the
     Bowen-York tensor alone.  momentum_net: the three means a projected
-    periodic momentum solve removed from S_i (NLResult.momentum_net[-1]; one
-    level): the report also carries the norms of Mom_i + m_i psi_0^-6.
+    periodic momentum solve removed from S_i (NLResult.momentum_net[-1]): the
+    report also carries the norms of Mom_i + m_i psi_0^-6, the offset added
+    cell by cell on every level.  reflux: the geometry-only AMRSolver of a
+    hierarchy's norms is built with it, as the solve's are (the norms do not
+    depend on it).
 
     On one level the norms are the operator's norm(x, 0) and norm(x, 2) *
     dx^1.5; over a hierarchy AMRSolver.computeNorm, so covered coarse cells
@@ -238,7 +241,7 @@ def constraints(psi, prm, phi0=None, punctures=None, matter=None,
         for l in range(len(grids)):
             a[l].set_zero()
             b[l].set_val(1.0)
-        geom = AMRSolver(list(zip(grids, a, b)), OperatorParams(), SolverParams())
+        geom = AMRSolver(list(zip(grids, a, b)), OperatorParams(), SolverParams(), reflux=reflux)
         per = [[lev.fields()[c] for lev in rep.fields] for c in range(5)]
         mx = [geom.computeNorm(x, 0) for x in per]
         l2 = [geom.computeNorm(x, 2) for x in per[:4]]
@@ -246,19 +249,27 @@ def constraints(psi, prm, phi0=None, punctures=None, matter=None,
     rep.l2_norm = dict(zip(COMPONENTS, l2))
     rep.max_ham_abs = mx[4]
     if momentum_net is not None:
-        if len(grids) != 1:
-            raise ValueError("momentum_net= needs one level")
         from .output import grchombo_vars
-        grid, dx = grids[0], grids[0].dx
         rep.momentum_net = [float(m) for m in momentum_net]
-        # psi_0^-6 = chi^1.5, chi the output's own component 0
-        w = [grchombo_vars(psis[0], n, bh, phi=phis[0] if phis is not None else None,
-                           punctures=punct, matter=mat)[0] ** 1.5 for n in range(grid.num_local)]
-        tmp = LevelData(grid)
-        tmp.set_zero()
+        # psi_0^-6 = chi^1.5, chi the output's own component 0 (which no matter
+        # enters; on a hierarchy the call without it takes any level's layout)
+        one = len(grids) == 1
+        w = [[grchombo_vars(psis[l], n, bh, phi=phis[l] if phis is not None else None,
+                            punctures=punct, matter=mat if one else None)[0] ** 1.5
+              for n in range(g.num_local)]
+             for l, g in enumerate(grids)]
+        tmp = [LevelData(g) for g in grids]
+        for f in tmp:
+            f.set_zero()
         for i, c in enumerate(COMPONENTS[1:]):
-            for n in range(grid.num_local):
-                tmp.upload(n, rep.fields[0].fields()[1 + i].download(n) + rep.momentum_net[i] * w[n])
-            rep.max_norm_net[c] = _field_norm(tmp, 0)
-            rep.l2_norm_net[c] = _field_norm(tmp, 2) * dx ** 1.5
+            for l, g in enumerate(grids):
+                for n in range(g.num_local):
+                    tmp[l].upload(n, rep.fields[l].fields()[1 + i].download(n)
+                                  + rep.momentum_net[i] * w[l][n])
+            if len(grids) == 1:
+                rep.max_norm_net[c] = _field_norm(tmp[0], 0)
+                rep.l2_norm_net[c] = _field_norm(tmp[0], 2) * grids[0].dx ** 1.5
+            else:
+                rep.max_norm_net[c] = geom.computeNorm(tmp, 0)
+                rep.l2_norm_net[c] = geom.computeNorm(tmp, 2)
     return rep

@@ -754,11 +754,20 @@ class AMRSolver:
     """AMR levels > 0: levels = [(grid, aCoef, bCoef), ...]
     from the coarsest; each finer grid is Grid(..., patches=True) on the
     coarser domain refined by 2, properly nested.  The [Chombo] AMRPoissonOp
-    multi-level operators (QuadCFInterp, AMROperator/AMRResidual with reflux a
-    no-op, AMRRestrict, AMRProlong, AMRUpdateResidual) and AMRMultiGrid's
-    multi-level V-cycle; level 0 is solved by its own MultiGrid (params)."""
+    multi-level operators (QuadCFInterp, AMROperator/AMRResidual, AMRRestrict,
+    AMRProlong, AMRUpdateResidual) and AMRMultiGrid's multi-level V-cycle;
+    level 0 is solved by its own MultiGrid (params).
 
-    def __init__(self, levels, op_params: OperatorParams, params: Optional[SolverParams] = None):
+    reflux=False: the reference's composite operator (reflux a no-op; not
+    conservative at coarse-fine faces).  reflux=True: applyOp, the residuals,
+    the preconditioner and the solve add the reflux term (the
+    kernel of libmgic_reflux.so, loaded here), and applyOp and the residuals
+    first overwrite the covered cells of their input with the finer level's
+    average, so the result depends on uncovered cells alone; with one level the switch
+    changes nothing and loads nothing."""
+
+    def __init__(self, levels, op_params: OperatorParams, params: Optional[SolverParams] = None,
+                 reflux: bool = False):
         self.levels = list(levels)
         n = len(self.levels)
         grids = (ctypes.c_void_p * n)(*[g.handle.value for g, _, _ in self.levels])
@@ -772,10 +781,24 @@ class AMRSolver:
              ctypes.byref(h))
         self._h = h
         self.num_levels = n
+        self.reflux_on = bool(reflux) and n > 1
+        if self.reflux_on:
+            _lib.reflux_lib()  # registers the launcher with libmgic
+            call("mgic_amr_set_reflux", self._h, 1)
 
     @property
     def handle(self):
         return self._h
+
+    def reflux(self, level: int, target: LevelData, phi_coarse: Optional[LevelData],
+               phi_fine: LevelData, sign: int = 1) -> None:
+        """the reflux term of `level` (which has a finer level), whatever the
+        switch: target +/-= (-beta b) * sum over the interface faces of
+        (<G_f> - G_c) / dx; phi_coarse None: a zero coarse field.  phi_fine's
+        ghosts and phi_coarse's face ghosts as AMROperator leaves them."""
+        _lib.reflux_lib()
+        call("mgic_amr_reflux", self._h, int(level), target.handle, self._f(phi_coarse),
+             phi_fine.handle, int(sign))
 
     @staticmethod
     def _f(x):
@@ -837,6 +860,12 @@ class AMRSolver:
     def applyOp(self, lhs, x, homogeneous: bool = True) -> None:
         call("mgic_amr_apply_op", self._h, self._fields(lhs), self._fields(x),
              int(bool(homogeneous)))
+
+    def residual(self, r, phi, rhs, homogeneous: bool = False) -> None:
+        """r = rhs - L(phi) over the hierarchy (the solve's own residual),
+        covered coarse cells zeroed"""
+        call("mgic_amr_composite_residual", self._h, self._fields(r), self._fields(phi),
+             self._fields(rhs), int(bool(homogeneous)))
 
     def dotProduct(self, x, y) -> float:
         out = ctypes.c_double()

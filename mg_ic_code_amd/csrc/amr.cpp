@@ -133,6 +133,185 @@ void CFLevel::zeroCovered(LevelData &crs, hipStream_t st) {
   down_plan->execute(*coarse->comm, stage->d_tab, crs.d_tab, st);
 }
 
+// ------------------------------------------------------------ flux register
+namespace {
+
+const mgic_reflux_table *g_reflux_table = nullptr;
+
+// r minus c as up to six disjoint boxes (slabs below / above c in x, then y
+// within c's x range, then z)
+void subtract(Box r, const Box &c, std::vector<Box> &out) {
+  if (r.intersect(c).empty()) {
+    out.push_back(r);
+    return;
+  }
+  for (int d = 0; d < 3; ++d) {
+    if (r.lo[d] < c.lo[d]) {
+      Box s = r;
+      s.hi[d] = c.lo[d] - 1;
+      out.push_back(s);
+      r.lo[d] = c.lo[d];
+    }
+    if (r.hi[d] > c.hi[d]) {
+      Box s = r;
+      s.lo[d] = c.hi[d] + 1;
+      out.push_back(s);
+      r.hi[d] = c.hi[d];
+    }
+  }
+}
+
+struct FaceRec {
+  int cbox;
+  long long coff;
+  int face;
+  mgic_reflux_face f;
+};
+
+long stride(const FabGeom &g, int d) { return d == 0 ? 1 : d == 1 ? g.sy : g.sz; }
+
+std::vector<int> local_index(const Grid &g) {
+  std::vector<int> at(g.boxes.size(), -1);
+  for (int n = 0; n < g.nlocal(); ++n) at[g.local[n]] = n;
+  return at;
+}
+
+}  // namespace
+
+void set_reflux_table(const mgic_reflux_table *t) { g_reflux_table = t; }
+const mgic_reflux_table *reflux_table() { return g_reflux_table; }
+
+FluxRegister::FluxRegister(const CFLevel &cf) {
+  const Grid &fine = *cf.fine, &coarse = *cf.coarse, &cfine = *cf.cfine;
+  MGIC_CHECK(fine.nlocal() == (int)fine.boxes.size() && coarse.nlocal() == (int)coarse.boxes.size(),
+             "reflux: every box of levels l and l + 1 must be local");
+  const std::vector<int> flocal = local_index(fine), clocal = local_index(coarse);
+  std::vector<FaceRec> recs;
+  for (size_t gi = 0; gi < fine.boxes.size(); ++gi) {
+    const Box &fb = fine.boxes[gi], &cb = cfine.boxes[gi];
+    const FabGeom &fg = fine.geom[flocal[gi]];
+    for (int dir = 0; dir < 3; ++dir) {
+      const int t0 = dir == 0 ? 1 : 0, t1 = dir == 2 ? 1 : 2;  // lower, higher tangential
+      for (int side = 0; side < 2; ++side) {
+        const bool at_domain = side ? cb.hi[dir] == coarse.domain.hi[dir]
+                                    : cb.lo[dir] == coarse.domain.lo[dir];
+        if (at_domain && !coarse.periodic[dir]) continue;  // the physical BC's face
+        // the coarse cells just outside the face, through the wrap
+        Box layer = cb.adj_cell(dir, side);
+        int sh[3] = {0, 0, 0};
+        if (at_domain) sh[dir] = side ? -coarse.domain.size(dir) : coarse.domain.size(dir);
+        layer = layer.shifted(sh);
+        std::vector<Box> open{layer}, next;
+        for (const Box &c : cfine.boxes) {  // ... that the fine level does not cover
+          next.clear();
+          for (const Box &r : open) subtract(r, c, next);
+          open.swap(next);
+        }
+        for (const Box &r : open)
+          for (size_t cj = 0; cj < coarse.boxes.size(); ++cj) {
+            const Box x = r.intersect(coarse.boxes[cj]);
+            if (x.empty()) continue;
+            const FabGeom &cg = coarse.geom[clocal[cj]];
+            for (int k = x.lo[2]; k <= x.hi[2]; ++k)
+              for (int j = x.lo[1]; j <= x.hi[1]; ++j)
+                for (int i = x.lo[0]; i <= x.hi[0]; ++i) {
+                  const int ci[3] = {i, j, k};
+                  int fi[3];  // the fine in-cell (0, 0) behind the face
+                  fi[dir] = side ? fb.hi[dir] : fb.lo[dir];
+                  fi[t0] = 2 * ci[t0];
+                  fi[t1] = 2 * ci[t1];
+                  FaceRec q;
+                  q.cbox = clocal[cj];
+                  q.coff = cg.offset(i, j, k);
+                  // the fine box's hi face is the lo face of the cell outside it
+                  q.face = 2 * dir + (side ? 0 : 1);
+                  q.f.foff = fg.offset(fi[0], fi[1], fi[2]);
+                  q.f.cstep = side ? -stride(cg, dir) : stride(cg, dir);
+                  q.f.fstep = side ? stride(fg, dir) : -stride(fg, dir);
+                  q.f.ft0 = stride(fg, t0);
+                  q.f.ft1 = stride(fg, t1);
+                  q.f.fbox = flocal[gi];
+                  q.f.pad = 0;
+                  recs.push_back(q);
+                }
+          }
+      }
+    }
+  }
+  std::sort(recs.begin(), recs.end(), [](const FaceRec &a, const FaceRec &b) {
+    if (a.cbox != b.cbox) return a.cbox < b.cbox;
+    if (a.coff != b.coff) return a.coff < b.coff;
+    return a.face < b.face;
+  });
+  std::vector<mgic_reflux_cell> cells;
+  std::vector<mgic_reflux_face> faces;
+  for (const FaceRec &q : recs) {
+    if (cells.empty() || cells.back().box != q.cbox || cells.back().off != q.coff)
+      cells.push_back(mgic_reflux_cell{q.coff, q.cbox, (int)faces.size(), 0, 0});
+    MGIC_CHECK(!(cells.back().mask & (1 << q.face)), "reflux: a face is listed twice");
+    cells.back().mask |= 1 << q.face;
+    faces.push_back(q.f);
+  }
+  ncell = (long long)cells.size();
+  nface = (long long)faces.size();
+  if (ncell == 0) return;
+  MGIC_HIP(hipMalloc(&d_cells, sizeof(mgic_reflux_cell) * cells.size()));
+  MGIC_HIP(hipMalloc(&d_faces, sizeof(mgic_reflux_face) * faces.size()));
+  MGIC_HIP(hipMemcpy(d_cells, cells.data(), sizeof(mgic_reflux_cell) * cells.size(),
+                     hipMemcpyHostToDevice));
+  MGIC_HIP(hipMemcpy(d_faces, faces.data(), sizeof(mgic_reflux_face) * faces.size(),
+                     hipMemcpyHostToDevice));
+}
+
+FluxRegister::~FluxRegister() {
+  if (d_cells) (void)hipFree(d_cells);
+  if (d_faces) (void)hipFree(d_faces);
+}
+
+void AMRSolver::setReflux(bool on) {
+  if (on && numLevels() > 1) {
+    if (!g_reflux_table)
+      throw Error(kState, "reflux: no launcher registered (libmgic_reflux.so, mgic_reflux_register)");
+    for (int l = 1; l < numLevels(); ++l)
+      if (!L_[l].flux) L_[l].flux = std::make_unique<FluxRegister>(*L_[l].cf);
+  }
+  reflux_ = on && numLevels() > 1;
+}
+
+void AMRSolver::reflux(int l, LevelData &target, const LevelData *phiC, const LevelData &phiF,
+                       int sign) {
+  MGIC_CHECK(l >= 0 && l + 1 < numLevels(), "reflux needs a finer level");
+  if (!g_reflux_table)
+    throw Error(kState, "reflux: no launcher registered (libmgic_reflux.so, mgic_reflux_register)");
+  Level &F = L_[l + 1];
+  if (!F.flux) F.flux = std::make_unique<FluxRegister>(*F.cf);
+  check_same_layout(*L_[l].grid, target, "reflux target");
+  if (phiC) check_same_layout(*L_[l].grid, *phiC, "reflux phi_coarse");
+  check_same_layout(*F.grid, phiF, "reflux phi_fine");
+  MGIC_CHECK(phiC != &target, "reflux: target and phi_coarse are one field");
+  if (F.flux->ncell == 0) return;
+  VariableCoeffPoissonOperator &o = op(l);
+  const int st = g_reflux_table->apply(F.flux->d_cells, F.flux->d_faces, F.flux->ncell, target.d_tab,
+                                       phiC ? phiC->d_tab : nullptr, phiF.d_tab, o.m_bCoef->d_tab,
+                                       -o.m_beta, L_[l].grid->dx, F.grid->dx, sign, o.stream());
+  if (st < 0) {
+    const char *m = g_reflux_table->last_error ? g_reflux_table->last_error() : nullptr;
+    throw Error(st, std::string("reflux: ") + (m ? m : "launcher error"));
+  }
+}
+
+static_assert(sizeof(mgic_reflux_cell) == 24 && sizeof(mgic_reflux_face) == 48,
+              "the rows libmgic_reflux.so reads (include/mgic.h)");
+
+void AMRSolver::averageCovered(std::vector<LevelData *> &x) {
+  for (int l = numLevels() - 1; l > 0; --l) L_[l].cf->averageDown(*x[l - 1], *x[l], op(l).stream());
+}
+
+void AMRSolver::refluxAll(std::vector<LevelData *> &target, std::vector<LevelData *> &phi,
+                          int sign) {
+  for (int l = 0; l + 1 < numLevels(); ++l) reflux(l, *target[l], phi[l], *phi[l + 1], sign);
+}
+
 // ------------------------------------------------------------------ solver
 void AMRSolver::define(const std::vector<AMRLevelSpec> &levels, const OpParams &prm,
                        const MGParams &base) {
@@ -171,7 +350,7 @@ void AMRSolver::AMROperator(int l, LevelData &Lphi, LevelData &phi, const LevelD
                             bool hom) {
   VariableCoeffPoissonOperator &o = op(l);
   if (l > 0) L_[l].cf->interp(phi, phiC, o.stream());  // [Chombo] coarseFineInterp
-  o.applyOpI(Lphi, phi, hom);                           // reflux: a no-op (.cpp:264-271)
+  o.applyOpI(Lphi, phi, hom);  // reflux: a no-op here (.cpp:264-271); applyOp adds it if switched on
 }
 
 void AMRSolver::AMRResidual(int l, LevelData &r, LevelData &phi, const LevelData *phiC,
@@ -214,6 +393,9 @@ void AMRSolver::cycle(int l) {
   // covered coarse cells
   F.op->relaxFromZero(*F.corr, *F.res, mgp_.n_pre);
   AMRRestrict(l, *C.res, *F.res, *F.corr, nullptr);
+  // the coarse residual of the correction next to the interface: the fine
+  // correction's flux against a zero coarse correction
+  if (reflux_) reflux(l - 1, *C.res, nullptr, *F.corr, -1);
   cycle(l - 1);
   // upsweep: e += P(e_c), r -= L(e) with the CF ghosts of e from e_c, smooth
   // the rest and add
@@ -224,11 +406,14 @@ void AMRSolver::cycle(int l) {
 }
 
 double AMRSolver::initResidual(std::vector<LevelData *> &phi, const std::vector<LevelData *> &rhs,
-                               int normType) {
+                               int normType, bool averaged) {
   const int n = numLevels();
   MGIC_CHECK((int)phi.size() == n && (int)rhs.size() == n, "AMR: one field per level");
+  if (reflux_ && !averaged) averageCovered(phi);
   for (int l = 0; l < n; ++l)
     AMRResidual(l, *L_[l].res, *phi[l], l ? phi[l - 1] : nullptr, *rhs[l], false);
+  if (reflux_)
+    for (int l = 0; l + 1 < n; ++l) reflux(l, *L_[l].res, phi[l], *phi[l + 1], -1);
   for (int l = 1; l < n; ++l) L_[l].cf->zeroCovered(*L_[l - 1].res, op(l).stream());
   if (normType < 0) return -1.0;
   double m = 0.0;
@@ -242,7 +427,7 @@ double AMRSolver::iteration(std::vector<LevelData *> &phi, const std::vector<Lev
   cycle(n - 1);
   for (int l = 0; l < n; ++l) op(l).incr(*phi[l], *L_[l].corr, 1.0);
   for (int l = n - 1; l > 0; --l) L_[l].cf->averageDown(*phi[l - 1], *phi[l], op(l).stream());
-  return initResidual(phi, rhs, normType);
+  return initResidual(phi, rhs, normType, true);  // phi was averaged down just above
 }
 
 // ------------------------------------------------ MultilevelLinearOp + BiCGStab
@@ -255,10 +440,13 @@ void AMRSolver::zeroCovered(std::vector<LevelData *> &x) {
   for (int l = 1; l < numLevels(); ++l) L_[l].cf->zeroCovered(*x[l - 1], op(l).stream());
 }
 
-void AMRSolver::applyOp(std::vector<LevelData *> &lhs, std::vector<LevelData *> &x, bool hom) {
+void AMRSolver::applyOp(std::vector<LevelData *> &lhs, std::vector<LevelData *> &x, bool hom,
+                        bool averaged) {
   const int n = numLevels();
   MGIC_CHECK((int)lhs.size() == n && (int)x.size() == n, "AMR: one field per level");
+  if (reflux_ && !averaged) averageCovered(x);
   for (int l = 0; l < n; ++l) AMROperator(l, *lhs[l], *x[l], l ? x[l - 1] : nullptr, hom);
+  if (reflux_) refluxAll(lhs, x, +1);
   zeroCovered(lhs);
 }
 
@@ -267,7 +455,9 @@ void AMRSolver::residual(std::vector<LevelData *> &r, std::vector<LevelData *> &
   const int n = numLevels();
   MGIC_CHECK((int)r.size() == n && (int)phi.size() == n && (int)rhs.size() == n,
              "AMR: one field per level");
+  if (reflux_) averageCovered(phi);
   for (int l = 0; l < n; ++l) AMRResidual(l, *r[l], *phi[l], l ? phi[l - 1] : nullptr, *rhs[l], hom);
+  if (reflux_) refluxAll(r, phi, -1);
   zeroCovered(r);
 }
 
@@ -349,6 +539,10 @@ void AMRSolver::precondition(std::vector<LevelData *> &e, const std::vector<Leve
       if (i == 0) op(l).assignLocal(*L_[l].res, *r[l]);
       else AMRResidual(l, *L_[l].res, *e[l], l ? e[l - 1] : nullptr, *r[l], true);
     }
+    // (e's covered cells are the finer level's average already: the end of
+    // the iteration before)
+    if (i > 0 && reflux_)
+      for (int l = 0; l + 1 < n; ++l) reflux(l, *L_[l].res, e[l], *e[l + 1], -1);
     if (i > 0)
       for (int l = 1; l < n; ++l) L_[l].cf->zeroCovered(*L_[l - 1].res, op(l).stream());
     cycle(n - 1);
@@ -402,7 +596,7 @@ int AMRSolver::solve(std::vector<LevelData *> &phi, const std::vector<LevelData 
       });
     }
     precondition(PT, P, iters);
-    applyOp(V, PT, true);
+    applyOp(V, PT, true, true);  // precondition() ends with averageDown
     const double m = dotProduct(RT, V);
     if (std::fabs(m) > prm.small * std::fabs(rho1)) {
       alpha = rho1 / m;
@@ -415,7 +609,7 @@ int AMRSolver::solve(std::vector<LevelData *> &phi, const std::vector<LevelData 
       nrm = nt == 0 || nt == 1 ? s : std::sqrt(s);
       if (nrm <= prm.eps * init_norm || nrm <= prm.reps) break;
       precondition(ST, S, iters);
-      applyOp(T, ST, true);
+      applyOp(T, ST, true, true);
       double ts = 0.0, tt = 0.0;
       each([&](int l, VariableCoeffPoissonOperator &o) {
         double a = 0.0, b = 0.0;

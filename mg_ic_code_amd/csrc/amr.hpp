@@ -4,7 +4,8 @@
 // The reference's operator inherits these from [Chombo] AMRPoissonOp (not in
 // the tree): QuadCFInterp / homogeneousCFInterp (called by the reference at
 // VariableCoeffPoissonOperator.cpp:156,296), AMROperator / AMRResidual (reflux
-// is a no-op in the reference, .cpp:264-271), AMRRestrict (CoarseAverage of
+// is a no-op in the reference, .cpp:264-271; here a switch, setReflux, off by
+// default), AMRRestrict (CoarseAverage of
 // the fine residual of the correction onto the covered coarse cells),
 // AMRProlong (piecewise constant), AMRUpdateResidual, and AMRMultiGrid's
 // multi-level cycle, for the refinement ratio 2 the factory's AMRnewOp sets
@@ -13,6 +14,7 @@
 // oracle/amr.py.
 #pragma once
 
+#include "../../include/mgic.h"  // mgic_reflux_cell / _face / _table
 #include "op.hpp"
 
 namespace mgic {
@@ -40,6 +42,25 @@ struct CFLevel {
   void prolongConstant(LevelData &fine, const LevelData &coarse, hipStream_t st);
   void zeroCovered(LevelData &coarse, hipStream_t st);
 };
+
+// The flux register of one coarse-fine pair: every cell of the
+// coarse level that the fine level does not cover and that has a covered
+// face neighbour (through the wrap where periodic, never across a domain
+// face), with the fine cells behind each such face.  Device tables for
+// libmgic_reflux.so's kernel; every box of both levels must be local.
+struct FluxRegister {
+  explicit FluxRegister(const CFLevel &cf);
+  ~FluxRegister();
+  FluxRegister(const FluxRegister &) = delete;
+  FluxRegister &operator=(const FluxRegister &) = delete;
+  mgic_reflux_cell *d_cells = nullptr;
+  mgic_reflux_face *d_faces = nullptr;
+  long long ncell = 0, nface = 0;
+};
+
+// the launcher of libmgic_reflux.so (mgic_amr_reflux_register); null until then
+void set_reflux_table(const mgic_reflux_table *t);
+const mgic_reflux_table *reflux_table();
 
 struct AMRLevelSpec {
   std::shared_ptr<Grid> grid;
@@ -71,23 +92,50 @@ class AMRSolver {
   // coarse cells zeroed) -> its norm (max over levels, if normType >= 0);
   // an iteration = one AMR V-cycle on the residuals, phi += e on every
   // level, average phi down, new residuals
+  // (averaged: phi's covered cells hold the finer level's average already --
+  // reflux's averaging of the input is skipped; iteration() says so)
   double initResidual(std::vector<LevelData *> &phi, const std::vector<LevelData *> &rhs,
-                      int normType);
+                      int normType, bool averaged = false);
   double iteration(std::vector<LevelData *> &phi, const std::vector<LevelData *> &rhs,
                    int normType);
   LevelData &residual(int l) { return *L_[l].res; }
+
+  // ---- reflux.  Off: the reference's composite operator.
+  // On: applyOp, residual, initResidual and precondition's residuals add the
+  // term on every level with a finer one (before the covered cells are
+  // zeroed), and the downsweep of cycle() subtracts the fine correction's
+  // from the restricted residual.  applyOp, residual and initResidual first
+  // write the average of the finer level into the covered cells of their
+  // input, finest pair first (averageDown; what every iteration leaves there
+  // anyway): the composite operator is then a function of the uncovered
+  // cells alone, bit for bit -- without it a covered value would cancel
+  // between the stencil and the term only up to rounding, and QuadCFInterp's
+  // second fine cell may be one the next level covers.  The averaging is one
+  // k_average launch per fine box and one copy per pair of levels (unlike the
+  // term's launches it grows with the number of boxes), so the callers that
+  // know their vector is in that state skip it: iteration()'s residual, and
+  // solve()'s operator applications on what precondition() returns.  With one
+  // level nothing changes.
+  void setReflux(bool on);
+  bool refluxOn() const { return reflux_; }
+  // level l (has a finer level): target +/-= ((-beta) b) * sum over the
+  // interface faces of (<G_f> - G_c) / dx_c; phiC == nullptr: a zero coarse
+  // field.  phiF's ghosts and phiC's face ghosts as AMROperator leaves them.
+  void reflux(int l, LevelData &target, const LevelData *phiC, const LevelData &phiF, int sign);
 
   // ---- MultilevelLinearOp<FArrayBox> over the hierarchy (Main_PoissonSolver.
   // cpp:103-117,169-184 with max_level > 0).  Vectors are one LevelData per
   // level.  [Chombo] semantics restated (MultilevelLinearOp is not in the
   // tree; parity unpinned, pinned to oracle/amr.py): the operator is
   // AMROperator on every level (CF ghosts from the next coarser level of the
-  // same vector, reflux a no-op) with the covered coarse cells of the result
+  // same vector, reflux a no-op unless setReflux) with the covered coarse cells of the result
   // zeroed, as the composite residual is; dot products and norms therefore
   // see only uncovered cells wherever one operand is an operator result or a
   // residual.  dotProduct = sum over levels of dx_l^3 * levelDot; norm 0 =
   // max over levels; norm 1 / 2 = the dx_l^3-weighted sum / root of sums.
-  void applyOp(std::vector<LevelData *> &lhs, std::vector<LevelData *> &x, bool hom);
+  // (averaged: as initResidual's; solve() passes the preconditioner's output)
+  void applyOp(std::vector<LevelData *> &lhs, std::vector<LevelData *> &x, bool hom,
+               bool averaged = false);
   void residual(std::vector<LevelData *> &r, std::vector<LevelData *> &phi,
                 const std::vector<LevelData *> &rhs, bool hom);
   double dotProduct(const std::vector<LevelData *> &x, const std::vector<LevelData *> &y);
@@ -118,7 +166,11 @@ class AMRSolver {
     std::unique_ptr<VariableCoeffPoissonOperator> op;  // levels > 0
     std::shared_ptr<CFLevel> cf;                       // levels > 0
     std::unique_ptr<LevelData> corr, res, dcorr, tmp;
+    std::unique_ptr<FluxRegister> flux;  // levels > 0: with the next coarser level (on first use)
   };
+  bool reflux_ = false;
+  void refluxAll(std::vector<LevelData *> &target, std::vector<LevelData *> &phi, int sign);
+  void averageCovered(std::vector<LevelData *> &x);  // covered cells <- the finer level's average
   std::vector<Level> L_;
   VariableCoeffPoissonOperatorFactory fac0_;
   MultiGrid base_;  // level 0's MG hierarchy (the l_base solve)

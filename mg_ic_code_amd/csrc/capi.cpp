@@ -1868,6 +1868,30 @@ MGIC_API int mgic_amr_residual(mgic_amr a, int level, mgic_field r, mgic_field p
                        h != 0);
   });
 }
+MGIC_API int mgic_amr_reflux_register(const mgic_reflux_table *t) {
+  return guard([&] {
+    NEED(t);
+    MGIC_CHECK(t->version == 1 && t->apply, "reflux table: version 1 with an apply entry");
+    set_reflux_table(t);
+  });
+}
+MGIC_API int mgic_amr_set_reflux(mgic_amr a, int on) {
+  return guard([&] {
+    NEED(a);
+    a->amr.setReflux(on != 0);
+  });
+}
+MGIC_API int mgic_amr_reflux(mgic_amr a, int level, mgic_field target, mgic_field phi_coarse,
+                             mgic_field phi_fine, int sign) {
+  return guard([&] {
+    NEED(a);
+    NEED(target);
+    NEED(phi_fine);
+    MGIC_CHECK(level >= 0 && level + 1 < a->amr.numLevels(), "reflux needs a finer level");
+    MGIC_CHECK(sign != 0, "reflux: sign is positive (an operator) or negative (a residual)");
+    a->amr.reflux(level, *target->f, phi_coarse ? phi_coarse->f.get() : nullptr, *phi_fine->f, sign);
+  });
+}
 MGIC_API int mgic_amr_restrict(mgic_amr a, int level, mgic_field res_coarse, mgic_field res,
                                mgic_field corr, mgic_field corr_coarse) {
   return guard([&] {
@@ -1948,6 +1972,18 @@ MGIC_API int mgic_amr_apply_op(mgic_amr a, const mgic_field *lhs, const mgic_fie
     auto l = amr_fields(a, lhs);
     auto v = amr_fields(a, x);
     a->amr.applyOp(l, v, homogeneous != 0);
+  });
+}
+MGIC_API int mgic_amr_composite_residual(mgic_amr a, const mgic_field *r, const mgic_field *phi,
+                                         const mgic_field *rhs, int homogeneous) {
+  return guard([&] {
+    NEED(a);
+    NEED(r);
+    NEED(phi);
+    NEED(rhs);
+    auto rv = amr_fields(a, r);
+    auto pv = amr_fields(a, phi);
+    a->amr.residual(rv, pv, amr_fields(a, rhs), homogeneous != 0);
   });
 }
 MGIC_API int mgic_amr_dot(mgic_amr a, const mgic_field *x, const mgic_field *y, double *out) {

@@ -94,7 +94,7 @@ class VariableCoeffPoissonOperator {
                 double beta);
   void resetLambda();
   void computeLambda();
-  void reflux() {}   // not implemented in the reference either (.cpp:264-271)
+  void reflux() {}   // empty as in the reference (.cpp:264-271); AMRSolver::reflux is the term (amr.hpp)
   void getFlux() {}  // (.cpp:389-397)
   void setTime(double t);
   void relax(LevelData &e, const LevelData &r, int iterations);  // [Chombo] AMRPoissonOp::relax

@@ -62,9 +62,14 @@ host in double, and the subtraction k_zm_shift of libmgic_zm.so
 net momentum density the torus cannot carry; they are recorded
 (MomentumSolver.removed, NLResult.momentum_net).  The ghosts of every field
 across a periodic face come from the exchange; fillBC and the extrapolation
-have nothing to do there.  A periodic hierarchy is refused: the AMR operators
-do no refluxing, so the composite operator's columns do not sum to zero and a
-zero-sum right-hand side is not in its range.
+have nothing to do there.  A periodic hierarchy is refused unless the solve
+runs with reflux (poisson_solve(..., reflux=True)): without it
+the AMR operators do no refluxing, so the composite operator's columns do not
+sum to zero and a zero-sum right-hand side is not in its range.  With it the
+projection is composite: m = computeSum(f) / computeSum(ones) over the
+uncovered cells of every level with dx_l^3 weights, subtracted from the valid
+cells of every level (k_zm_shift per level; covered cells are shifted too,
+which nothing reads).
 """
 from __future__ import annotations
 
@@ -118,6 +123,16 @@ class MomentumFields:
         return self.LW[level]
 
 
+def resolve_reflux(reflux, prm) -> bool:
+    """poisson_solve's reflux: None -- the deck's reflux (absent: 0); True /
+    False / 1 / 0; anything else is a ValueError."""
+    if reflux is None:
+        reflux = getattr(prm, "reflux", 0)
+    if isinstance(reflux, bool) or (isinstance(reflux, int) and reflux in (0, 1)):
+        return bool(reflux)
+    raise ValueError(f"reflux must be 0 or 1 (False or True), got {reflux!r}")
+
+
 def resolve_zero_mode(zero_mode: Optional[str], prm) -> str:
     """poisson_solve's zero_mode: None -- the deck's momentum_zero_mode (absent:
     "refuse"); anything but the two accepted values is a ValueError."""
@@ -129,10 +144,11 @@ def resolve_zero_mode(zero_mode: Optional[str], prm) -> str:
 
 
 def check_momentum_request(mat, periodic: bool, func: str = "poisson_solve",
-                           zero_mode: str = "refuse", num_levels: int = 1) -> None:
+                           zero_mode: str = "refuse", num_levels: int = 1,
+                           reflux: bool = False) -> None:
     """The refusals of momentum=True, raised before anything is launched:
     no matter, a matter without a Pi_0, a periodic base without
-    zero_mode="project", a periodic hierarchy with it."""
+    zero_mode="project", a periodic hierarchy with it and without reflux."""
     if mat is None:
         raise MatterArgumentError(func, "momentum=True needs matter: the source of the momentum "
                                   "constraint is the scalar field's Pi d_i phi")
@@ -144,7 +160,7 @@ def check_momentum_request(mat, periodic: bool, func: str = "poisson_solve",
                          "alpha = 0 problem Lap V_i = S_i needs sum S_i = 0 over the domain, "
                          "which a varying psi_0 does not give; zero_mode='project' (the deck's "
                          "momentum_zero_mode = project) removes the mean of S_i and reports it")
-    if periodic and num_levels > 1:
+    if periodic and num_levels > 1 and not reflux:
         raise ValueError("zero_mode='project' on a periodic hierarchy is not supported: the AMR "
                          "operators do no refluxing, so the composite operator's columns do not "
                          "sum to zero and a zero-sum right-hand side is not in its range; use "
@@ -237,22 +253,28 @@ class MomentumSolver:
     """The operators of the four solves: -beta Lap with the deck's boundary
     conditions (aCoef = 0, bCoef = 1), the NL loop's multigrid and BiCGStab
     settings.  Nothing in them depends on psi, so they are built once.
-    zero_mode "project" on a periodic one-level base: every solve is projected
-    (the module's docstring), and `removed` keeps the mean taken out of each
+    zero_mode "project" on a periodic base: every solve is projected (the
+    module's docstring), and `removed` keeps the mean taken out of each
     right-hand side, in the order of the solves, until the caller clears it.
-    On a base that is not periodic zero_mode changes nothing."""
+    On a base that is not periodic zero_mode changes nothing.  reflux: the
+    hierarchy's AMRSolver is built with it (one level: no effect); a periodic
+    hierarchy is projected only with it."""
 
     def __init__(self, grids: Sequence[Grid], prm, op_params: OperatorParams, sp: SolverParams,
-                 zero_mode: str = "refuse"):
+                 zero_mode: str = "refuse", reflux: bool = False):
         self.grids = list(grids)
         self.prm = prm
         self.project = zero_mode == "project" and all(self.grids[0].periodic)
-        if self.project and len(self.grids) > 1:
-            raise ValueError("zero_mode='project' needs a one-level base")
+        if self.project and len(self.grids) > 1 and not reflux:
+            raise ValueError("zero_mode='project' needs a one-level base, or reflux")
         self.removed: List[float] = []
         self.source_max: List[float] = []
+        # per solve since the caller last cleared it: (the BiCGStab's final
+        # residual max norm, max|rhs| as the solve took it); (0.0, 0.0) for the
+        # all-zero shortcut
+        self.final_norms: List[tuple] = []
         self.ones = None
-        if self.project:
+        if self.project and len(self.grids) == 1:
             d = self.grids[0].domain
             self.cells = (d[3] - d[0] + 1) * (d[4] - d[1] + 1) * (d[5] - d[2] + 1)
             self.ones = LevelData(self.grids[0])
@@ -271,9 +293,15 @@ class MomentumSolver:
             mlop = MultilevelLinearOp(self.amg, prm.numMGIterations)
             self.ops = [self.amg.op(0)]
         else:
-            self.amr = AMRSolver(list(zip(self.grids, self.a, self.b)), op_params, sp)
+            self.amr = AMRSolver(list(zip(self.grids, self.a, self.b)), op_params, sp,
+                                 reflux=reflux)
             mlop = MultilevelLinearOp(self.amr, prm.numMGIterations)
             self.ops = [self.amr.level_op(l) for l in range(len(self.grids))]
+            if self.project:  # computeSum(ones): the hierarchy's volume
+                ones = [LevelData(g) for g in self.grids]
+                for f in ones:
+                    f.set_val(1.0)
+                self.volume = self.amr.computeSum(ones)
         self.solver = BiCGStabSolver(mlop, tolerance=prm.tolerance,
                                      max_iterations=prm.max_iterations, norm_type=0)
 
@@ -294,18 +322,32 @@ class MomentumSolver:
         shift(self.grids[0].comm, fields, means)
         return means
 
+    def _remove(self, xs: Sequence[List[LevelData]]) -> List[float]:
+        """Subtract its mean from each of one or three fields over the hierarchy
+        (xs[i]: one LevelData per level).  One level: remove_means.  More: the
+        composite mean computeSum(f) / computeSum(ones), subtracted from the
+        valid cells of every level (one pass of k_zm_shift per level)."""
+        if self.amr is None:
+            return self.remove_means([x[0] for x in xs])
+        means = [self.amr.computeSum(x) / self.volume for x in xs]
+        for l, g in enumerate(self.grids):
+            shift(g.comm, [x[l] for x in xs], means)
+        return means
+
     def _solve(self, x: List[LevelData], rhs: List[LevelData]) -> int:
         """The all-zero shortcut, the scaling by -beta and the solve."""
-        if self._max_norm(rhs) == 0.0:
+        rhs_max = self._max_norm(rhs)
+        if rhs_max == 0.0:
             for f in x:
                 f.set_zero()
+            self.final_norms.append((0.0, 0.0))
             return 0
         if self.rhs_scale != 1.0:
             for l, f in enumerate(rhs):
                 self.ops[l].scale(f, self.rhs_scale)
-        if self.amr is None:
-            return self.solver.solve(x[0], rhs[0])
-        return self.solver.solve(x, rhs)
+        its = self.solver.solve(x[0], rhs[0]) if self.amr is None else self.solver.solve(x, rhs)
+        self.final_norms.append((self.solver.final_norm, abs(self.rhs_scale) * rhs_max))
+        return its
 
     def _fill(self, x: List[LevelData]) -> None:
         for l, f in enumerate(x):
@@ -326,10 +368,10 @@ class MomentumSolver:
         zeros has the mean 0.0, stays as it is and takes it as before, and a
         constant one, which has no solution part either, takes it too."""
         if self.project:
-            self.removed.extend(self.remove_means(rhs))
+            self.removed.extend(self._remove([rhs]))
         its = self._solve(x, rhs)
         if self.project:
-            self.remove_means(x)
+            self._remove([x])
         self._fill(x)
         return its
 
@@ -340,10 +382,10 @@ class MomentumSolver:
         in another (k_zm_shift<3>); `source_max` keeps max|rhs_i| as they came."""
         if not self.project:
             return [self.solve(x, r) for x, r in zip(xs, rhss)]
-        self.source_max = [self.ops[0].norm(r[0], 0) for r in rhss]
-        self.removed.extend(self.remove_means([r[0] for r in rhss]))
+        self.source_max = [self._max_norm(r) for r in rhss]
+        self.removed.extend(self._remove(list(rhss)))
         its = [self._solve(x, r) for x, r in zip(xs, rhss)]
-        self.remove_means([x[0] for x in xs])
+        self._remove(list(xs))
         for x in xs:
             self._fill(x)
         return its

@@ -34,6 +34,10 @@ the outer BiCGStab over MultilevelLinearOp with AMR V-cycles as its
 preconditioner (:169-184; AMRSolver), then per level QuadCFInterp of dpsi
 from the coarser level before set_update_psi0 (:189-205), and computeNorm /
 computeSum over the hierarchy with covered cells masked (:144-145, :208).
+With reflux (the keyword, or the deck's reflux = 1) every AMRSolver of the
+solve adds the reflux term at the coarse-fine faces: the
+composite operator is then conservative, and a periodic hierarchy takes the
+projected momentum solve.
 """
 from __future__ import annotations
 
@@ -50,8 +54,8 @@ from ._lib import call
 from .constraints import constraints as constraint_report
 from .output import output_final_data, output_solver_data
 from .matter import fill_matter, resolve_matter, set_nl_coefs_matter, set_nl_integrand_matter
-from .momentum import (MomentumFields, MomentumSolver, check_momentum_request, resolve_zero_mode,
-                       set_longitudinal, set_nl_coefs_ctt, set_nl_integrand_ctt,
+from .momentum import (MomentumFields, MomentumSolver, check_momentum_request, resolve_reflux,
+                       resolve_zero_mode, set_longitudinal, set_nl_coefs_ctt, set_nl_integrand_ctt,
                        solve_vector_potential)
 from .params import PoissonParameters
 from .phi import resolve_phi0, set_nl_coefs_phi, set_nl_integrand_phi
@@ -91,6 +95,10 @@ class NLResult:
     # the -beta scaling), and each divided by that iteration's max|S_i|
     momentum_net: List[List[float]] = field(default_factory=list)
     momentum_net_relative: List[List[float]] = field(default_factory=list)
+    # per NL iteration and momentum solve (V_x, V_y, V_z, U): (final residual
+    # max norm of the BiCGStab, max|rhs| as it took it); (0.0, 0.0) where the
+    # right-hand side was all zero
+    momentum_residuals: List[List[tuple]] = field(default_factory=list)
 
 
 def set_nl_integrand(psi: LevelData, out: LevelData, bh: dict) -> None:
@@ -136,7 +144,7 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
                   output_dir: Optional[str] = None, phi0=None, punctures=None,
                   matter=None, constraints: bool = False,
                   momentum: Optional[bool] = None,
-                  zero_mode: Optional[str] = None) -> NLResult:
+                  zero_mode: Optional[str] = None, reflux=None) -> NLResult:
     """phi0: None -- the analytic Gaussian, evaluated in the kernels; else a
     phi.PhiProfile, or one pre-filled LevelData per level: phi_0 is stored once
     before the NL loop (set_initial_conditions, SetLevelData.cpp:32-71) and the
@@ -166,22 +174,29 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
     mean of each of its four right-hand sides and solutions (momentum.py), the
     means removed from S_i are NLResult.momentum_net, and each NL iteration
     runs the momentum step first so that K comes from the total tensor; a
-    periodic hierarchy is refused (ValueError), and on a base that is not
-    periodic it changes nothing.  None: the deck's momentum_zero_mode; any
-    other value is a ValueError."""
+    periodic hierarchy is refused (ValueError) unless reflux is on, and on a
+    base that is not periodic it changes nothing.  None: the deck's
+    momentum_zero_mode; any other value is a ValueError.
+    reflux: True -- every AMRSolver the solve builds (the Hamiltonian solve,
+    the momentum solves, the geometry-only ones) adds the reflux term at the
+    coarse-fine faces, and the projection of the momentum solve
+    on a periodic hierarchy is the composite one (momentum.py); on one level
+    it changes nothing and loads nothing.  None: the deck's reflux (0 when
+    absent); anything but True / False / 1 / 0 is a ValueError."""
     punct = resolve_punctures(punctures, prm)
     zero_mode = resolve_zero_mode(zero_mode, prm)
+    reflux = resolve_reflux(reflux, prm)
     if momentum is None:
         momentum = bool(getattr(prm, "solve_momentum", 0))
     if momentum:  # refused before anything is stored or launched
         nlev = len(grid) if isinstance(grid, (list, tuple)) else 1
         check_momentum_request(resolve_matter(matter, prm), bool(prm.is_periodic),
-                               zero_mode=zero_mode, num_levels=nlev)
+                               zero_mode=zero_mode, num_levels=nlev, reflux=reflux)
     if isinstance(grid, (list, tuple)):
         if len(grid) > 1:
             return _poisson_solve_amr(list(grid), prm, max_depth, prolong_type, bottom_solver,
                                       max_NL_iterations, output_dir, phi0, punct, matter,
-                                      constraints, momentum)
+                                      constraints, momentum, zero_mode, reflux)
         grid = grid[0]
     mat = fill_matter(matter, [grid], prm)
     phis = resolve_phi0(phi0, [grid], prm)
@@ -219,7 +234,7 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
             # tensor.  S_i does not depend on K: mgic_field_momentum_source
             # (bh_constraints with `source`) reads constant_K for Ham alone,
             # which it does not write, so the order leaves S_i as it was
-            _momentum_step(res, msolve, mom, psi, bh, mat, punct, phis)
+            _momentum_step(res, msolve, mom, [psi], bh, mat, punct, phis)
         if periodic:  # integrability condition for K (:133-147)
             if integrand is None:
                 integrand, ones = LevelData(grid), LevelData(grid)
@@ -231,7 +246,7 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
             bh["constant_K"] = -math.sqrt(abs(integral) / volume)
             res.constant_K.append(bh["constant_K"])
         if momentum and not periodic:
-            _momentum_step(res, msolve, mom, psi, bh, mat, punct, phis)
+            _momentum_step(res, msolve, mom, [psi], bh, mat, punct, phis)
         _coefs(psi, phi, a, rhs, bh, punct, mat, 0, mom)  # :155-161
         fac = defineOperatorFactory(grid, a, b, op_params)
         # N > 1: depths whose boxes are below 32 cells a side are gathered to
@@ -271,11 +286,13 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
 
 
 def _momentum_step(res: NLResult, msolve, mom, psi, bh, mat, punct, phis) -> None:
-    """V_i and U at the current psi, then LW_ij of the total tensor; with the
-    zero mode projected, the means removed from S_i."""
+    """V_i and U at the current psi (one LevelData per level), then LW_ij of the
+    total tensor; with the zero mode projected, the means removed from S_i."""
     res.momentum_iterations.append(
-        solve_vector_potential(msolve, mom, [psi], bh, mat, punct, phis))
+        solve_vector_potential(msolve, mom, psi, bh, mat, punct, phis))
     set_longitudinal(msolve, mom)
+    res.momentum_residuals.append(list(msolve.final_norms))
+    msolve.final_norms.clear()
     if msolve.project:
         net = msolve.removed[:3]
         msolve.removed.clear()
@@ -295,7 +312,8 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
                        prolong_type: int, bottom_solver: int, max_NL_iterations: Optional[int],
                        output_dir: Optional[str], phi0=None, punct=None,
                        matter=None, constraints: bool = False,
-                       momentum: bool = False) -> NLResult:
+                       momentum: bool = False, zero_mode: str = "refuse",
+                       reflux: bool = False) -> NLResult:
     """poissonSolve over nlevels = len(grids) AMR levels (Main_PoissonSolver.cpp:51-250)."""
     periodic = bool(prm.is_periodic)
     if periodic != all(grids[0].periodic):
@@ -323,30 +341,34 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
     mom = msolve = None
     if momentum:
         mom = res.momentum = MomentumFields(grids)
-        msolve = MomentumSolver(grids, prm, op_params, sp)
+        msolve = MomentumSolver(grids, prm, op_params, sp, zero_mode, reflux=reflux)
     n_nl = prm.max_NL_iterations if max_NL_iterations is None else max_NL_iterations
     volume = prm.domainLength[0] * prm.domainLength[1] * prm.domainLength[2]
     integrand = geom = None
     refs = [2] * nlev
     for it in range(n_nl):
+        if momentum and periodic:
+            # the momentum step first, so that K below comes from the total
+            # tensor (as on one level: S_i does not depend on K)
+            _momentum_step(res, msolve, mom, psi, bh, mat, punct, phis)
         if periodic:  # integrability condition for K over the hierarchy (:137-150)
             if integrand is None:
                 integrand = [LevelData(g) for g in grids]
                 # computeSum only needs the hierarchy's geometry
-                geom = AMRSolver(list(zip(grids, a, b)), op_params, sp)
+                geom = AMRSolver(list(zip(grids, a, b)), op_params, sp, reflux=reflux)
             bh["constant_K"] = 0.0
             for l in range(nlev):
-                _integrand(psi[l], phi[l], integrand[l], bh, punct, mat, l)
+                _integrand(psi[l], phi[l], integrand[l], bh, punct, mat, l, mom)
             integral = geom.computeSum(integrand)
             bh["constant_K"] = -math.sqrt(abs(integral) / volume)
             res.constant_K.append(bh["constant_K"])
-        if momentum:  # V_i and U at the current psi, then LW_ij of the total tensor
+        if momentum and not periodic:  # V_i and U at the current psi, then LW_ij
             res.momentum_iterations.append(
                 solve_vector_potential(msolve, mom, psi, bh, mat, punct, phis))
             set_longitudinal(msolve, mom)
         for l in range(nlev):  # :154-160
             _coefs(psi[l], phi[l], a[l], rhs[l], bh, punct, mat, l, mom)
-        amr = AMRSolver(list(zip(grids, a, b)), op_params, sp)  # :163-170
+        amr = AMRSolver(list(zip(grids, a, b)), op_params, sp, reflux=reflux)  # :163-170
         solver = BiCGStabSolver(MultilevelLinearOp(amr, prm.numMGIterations),
                                 tolerance=prm.tolerance, max_iterations=prm.max_iterations,
                                 norm_type=0)
@@ -372,7 +394,9 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
                               punctures=punct, matter=mat, constraints=constraints, momentum=mom)
     finish_nl_loop(res, write)
     if constraints:
-        res.constraints = constraint_report(psi, bh, phis, punct, mat, momentum=mom)
+        res.constraints = constraint_report(
+            psi, bh, phis, punct, mat, momentum=mom,
+            momentum_net=res.momentum_net[-1] if res.momentum_net else None, reflux=reflux)
     return res
 
 

@@ -81,6 +81,11 @@ class PoissonParameters:
     # (momentum.py); absent: refuse.  It has no effect on a base that is not
     # periodic
     momentum_zero_mode: str = "refuse"
+    # reflux = 0|1 (not a key of the reference): 1 adds the reflux term at the
+    # coarse-fine faces to every multi-level operator of the solve (DESIGN.md
+    # 3l), which makes the composite operator conservative; absent: 0.  It has
+    # no effect on one level
+    reflux: int = 0
 
     # what getPoissonParameters derives besides (PoissonParameters.cpp:68, :78-79,
     # :111-128): one more level than max_level, ratio 2 on every level, the
@@ -202,6 +207,11 @@ def read_params(text: str, overrides: Optional[Dict[str, str]] = None) -> Poisso
         if zm not in ZERO_MODES:
             raise ValueError(f"momentum_zero_mode must be refuse or project, got {zm!r}")
         p.momentum_zero_mode = zm
+    rf = get("reflux", int, required=False)
+    if rf is not None:
+        if rf not in (0, 1):
+            raise ValueError(f"reflux must be 0 or 1, got {rf}")
+        p.reflux = rf
     return p
 
 
