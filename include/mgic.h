@@ -253,6 +253,18 @@ MGIC_API int mgic_regrid_levels(int nlev, const int domain0[6], const unsigned c
                                 const int *lat_lo, const int *lat_n, int block_factor,
                                 int max_grid_size, double fill_ratio, int nesting_radius, int cap,
                                 int *nbox, int *boxes, int *new_finest);
+/* The same with proper nesting through the wrap: in a
+ * direction with periodic[d] != 0 the nesting region coarsen(box of level
+ * l + 2, 2) +- nesting_radius is not clipped to the level-(l + 1) domain but
+ * wrapped round it before it is coarsened onto level l's lattice.
+ * Clustering runs inside the domain, so no box crosses a face: a feature on
+ * a periodic face becomes boxes on both sides.  periodic = (0, 0, 0) gives
+ * mgic_regrid_levels. */
+MGIC_API int mgic_regrid_levels_periodic(int nlev, const int domain0[6], const int periodic[3],
+                                         const unsigned char *const *masks, const int *lat_lo,
+                                         const int *lat_n, int block_factor, int max_grid_size,
+                                         double fill_ratio, int nesting_radius, int cap,
+                                         int *nbox, int *boxes, int *new_finest);
 /* LoadBalance stand-in: box i of the sorted list goes to rank
  * floor(size * (prefix_i + cells_i / 2) / total) */
 MGIC_API int mgic_regrid_owners(int nbox, const int *boxes, int size, int *owners);

@@ -114,6 +114,8 @@ SIGNATURES = {
     "mgic_regrid_cluster": [c_void_p, PI, c_double, c_int, c_int, PI, PI],
     "mgic_regrid_levels": [c_int, PI, POINTER(c_void_p), PI, PI, c_int, c_int, c_double, c_int,
                            c_int, PI, PI, PI],
+    "mgic_regrid_levels_periodic": [c_int, PI, PI, POINTER(c_void_p), PI, PI, c_int, c_int,
+                                    c_double, c_int, c_int, PI, PI, PI],
     "mgic_regrid_owners": [c_int, PI, c_int, PI],
     "mgic_op_update_psi": [H, H, H],
     "mgic_plan_create": [c_int, c_int, PI, PI, c_int, PI, PI, c_int, PI, PI, c_int, c_int, PH],
@@ -521,6 +523,47 @@ def reflux_call(name: str, *args) -> int:
     st = getattr(L, name)(*args)
     if st < 0:
         msg = L.mgic_reflux_last_error()
+        raise MgicError(name, st, msg.decode() if msg else "")
+    return st
+
+
+# ---- libmgic_ptag.so (include/mgic_ptag.h): the periodic tagging kernel of
+# set_grids, loaded on first use (grids.py, periodic_regrid on a base with a
+# periodic direction); missing or unloadable = an ImportError, no fallback
+PTAG_LIB_PATH = os.path.join(_HERE, "libmgic_ptag.so")
+PTAG_SIGNATURES = {
+    "mgic_ptag_last_error": [],
+    "mgic_ptag_lattice": [H, H, c_double, c_int, c_int, PI, PI, c_void_p],
+    "mgic_ptag_launch_ledger_dump": [c_char_p],
+    "mgic_ptag_launch_ledger_reset": [],
+}
+_ptag = None
+
+
+def ptag_lib() -> ctypes.CDLL:
+    global _ptag
+    if _ptag is None:
+        if not os.path.exists(PTAG_LIB_PATH):
+            raise ImportError(f"{PTAG_LIB_PATH} not found: build it with __graft_entry__.build()")
+        L = ctypes.CDLL(PTAG_LIB_PATH)
+        for name, argtypes in PTAG_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.argtypes = argtypes
+            fn.restype = c_char_p if name == "mgic_ptag_last_error" else c_int
+        _ptag = L
+    return _ptag
+
+
+def ptag_loaded() -> bool:
+    """Whether libmgic_ptag.so has been loaded by this process."""
+    return _ptag is not None
+
+
+def ptag_call(name: str, *args) -> int:
+    L = ptag_lib()
+    st = getattr(L, name)(*args)
+    if st < 0:
+        msg = L.mgic_ptag_last_error()
         raise MgicError(name, st, msg.decode() if msg else "")
     return st
 

@@ -1247,39 +1247,58 @@ MGIC_API int mgic_regrid_cluster(const unsigned char *mask, const int n[3], doub
     from_iboxes(v, cap, boxes);
   });
 }
+static void regrid_levels_capi(int nlev, const int domain0[6], const int *periodic,
+                               const unsigned char *const *masks, const int *lat_lo,
+                               const int *lat_n, int block_factor, int max_grid_size,
+                               double fill_ratio, int nesting_radius, int cap, int *nbox,
+                               int *boxes, int *new_finest) {
+  NEED(domain0);
+  NEED(masks);
+  NEED(lat_lo);
+  NEED(lat_n);
+  NEED(nbox);
+  NEED(new_finest);
+  MGIC_CHECK(nlev >= 1, "nlev must be >= 1");
+  MGIC_CHECK(nesting_radius >= 0, "nesting_radius must be >= 0");
+  MGIC_CHECK(cap == 0 || boxes != nullptr, "null argument: boxes");
+  std::vector<regrid::LevelTags> tags((size_t)nlev);
+  for (int l = 0; l < nlev; ++l) {
+    tags[l].mask = masks[l];
+    for (int d = 0; d < 3; ++d) {
+      tags[l].lat_lo[d] = lat_lo[3 * l + d];
+      tags[l].lat_n[d] = lat_n[3 * l + d];
+    }
+  }
+  const regrid::IBox dom = to_iboxes(1, domain0)[0];
+  std::vector<std::vector<regrid::IBox>> out;
+  std::string err;
+  MGIC_CHECK(regrid::regrid_levels(tags, dom, block_factor, max_grid_size, fill_ratio,
+                                   nesting_radius, &out, new_finest, &err, periodic) == 0, err);
+  int at = 0;
+  for (int l = 0; l < nlev; ++l) {
+    nbox[l] = (int)out[l].size();
+    if (at < cap) from_iboxes(out[l], cap - at, boxes + 6 * at);
+    at += nbox[l];
+  }
+}
 MGIC_API int mgic_regrid_levels(int nlev, const int domain0[6], const unsigned char *const *masks,
                                 const int *lat_lo, const int *lat_n, int block_factor,
                                 int max_grid_size, double fill_ratio, int nesting_radius, int cap,
                                 int *nbox, int *boxes, int *new_finest) {
   return guard([&] {
-    NEED(domain0);
-    NEED(masks);
-    NEED(lat_lo);
-    NEED(lat_n);
-    NEED(nbox);
-    NEED(new_finest);
-    MGIC_CHECK(nlev >= 1, "nlev must be >= 1");
-    MGIC_CHECK(nesting_radius >= 0, "nesting_radius must be >= 0");
-    MGIC_CHECK(cap == 0 || boxes != nullptr, "null argument: boxes");
-    std::vector<regrid::LevelTags> tags((size_t)nlev);
-    for (int l = 0; l < nlev; ++l) {
-      tags[l].mask = masks[l];
-      for (int d = 0; d < 3; ++d) {
-        tags[l].lat_lo[d] = lat_lo[3 * l + d];
-        tags[l].lat_n[d] = lat_n[3 * l + d];
-      }
-    }
-    const regrid::IBox dom = to_iboxes(1, domain0)[0];
-    std::vector<std::vector<regrid::IBox>> out;
-    std::string err;
-    MGIC_CHECK(regrid::regrid_levels(tags, dom, block_factor, max_grid_size, fill_ratio,
-                                     nesting_radius, &out, new_finest, &err) == 0, err);
-    int at = 0;
-    for (int l = 0; l < nlev; ++l) {
-      nbox[l] = (int)out[l].size();
-      if (at < cap) from_iboxes(out[l], cap - at, boxes + 6 * at);
-      at += nbox[l];
-    }
+    regrid_levels_capi(nlev, domain0, nullptr, masks, lat_lo, lat_n, block_factor, max_grid_size,
+                       fill_ratio, nesting_radius, cap, nbox, boxes, new_finest);
+  });
+}
+MGIC_API int mgic_regrid_levels_periodic(int nlev, const int domain0[6], const int periodic[3],
+                                         const unsigned char *const *masks, const int *lat_lo,
+                                         const int *lat_n, int block_factor, int max_grid_size,
+                                         double fill_ratio, int nesting_radius, int cap,
+                                         int *nbox, int *boxes, int *new_finest) {
+  return guard([&] {
+    NEED(periodic);
+    regrid_levels_capi(nlev, domain0, periodic, masks, lat_lo, lat_n, block_factor,
+                       max_grid_size, fill_ratio, nesting_radius, cap, nbox, boxes, new_finest);
   });
 }
 MGIC_API int mgic_regrid_owners(int nbox, const int *boxes, int size, int *owners) {

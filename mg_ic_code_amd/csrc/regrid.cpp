@@ -184,7 +184,8 @@ std::vector<IBox> cluster(const unsigned char *mask, const int n[3], double fill
 
 int regrid_levels(const std::vector<LevelTags> &tags, const IBox &domain0, int block_factor,
                   int max_grid_size, double fill_ratio, int nesting_radius,
-                  std::vector<std::vector<IBox>> *out, int *new_finest, std::string *err) {
+                  std::vector<std::vector<IBox>> *out, int *new_finest, std::string *err,
+                  const int *periodic) {
   int c = 1, maxlen = 1;
   if (!lattice_params(block_factor, max_grid_size, &c, &maxlen, err)) return -1;
   if (!(fill_ratio > 0.0)) {
@@ -226,21 +227,54 @@ int regrid_levels(const std::vector<LevelTags> &tags, const IBox &domain0, int b
   out->assign(nlev, std::vector<IBox>());
   for (int l = nlev - 1; l >= 0; --l) {
     // nesting: the lattice cells of level l under boxes[l + 2] grown by
-    // nesting_radius level-(l+1) cells
+    // nesting_radius level-(l+1) cells; clipped to the level-(l+1) domain, or
+    // in a periodic direction wrapped round it
     std::vector<IBox> nest;
     if (l + 1 < nlev)
       for (const IBox &f : (*out)[l + 1]) {
-        IBox b;
-        bool empty = false;
+        // per direction: the lattice intervals under the grown region; one
+        // when it is clipped, up to two when it wraps round a periodic domain
+        int nr[3] = {0, 0, 0}, rlo[3][2], rhi[3][2];
         for (int d = 0; d < 3; ++d) {
+          const int dlo = dom[l + 1].lo[d], dhi = dom[l + 1].hi[d], n = dhi - dlo + 1;
           int lo = fdiv(f.lo[d], 2) - nesting_radius, hi = fdiv(f.hi[d], 2) + nesting_radius;
-          lo = std::max(lo, dom[l + 1].lo[d]);
-          hi = std::min(hi, dom[l + 1].hi[d]);
-          if (hi < lo) empty = true;
-          b.lo[d] = fdiv(fdiv(lo, 2), c);
-          b.hi[d] = fdiv(fdiv(hi, 2), c);
+          auto add = [&](int a, int z) {
+            rlo[d][nr[d]] = fdiv(fdiv(a, 2), c);
+            rhi[d][nr[d]] = fdiv(fdiv(z, 2), c);
+            ++nr[d];
+          };
+          if (periodic && periodic[d]) {
+            if ((long)hi - lo + 1 >= n) {
+              add(dlo, dhi);
+            } else {
+              auto wrap = [&](int v) { return dlo + (int)((((long)v - dlo) % n + n) % n); };
+              lo = wrap(lo);
+              hi = wrap(hi);
+              if (lo <= hi) {
+                add(lo, hi);
+              } else {  // through the face: the two ends of the domain
+                add(dlo, hi);
+                add(lo, dhi);
+              }
+            }
+          } else {
+            lo = std::max(lo, dlo);
+            hi = std::min(hi, dhi);
+            if (hi >= lo) add(lo, hi);
+          }
         }
-        if (!empty) nest.push_back(b);
+        for (int k = 0; k < nr[2]; ++k)
+          for (int j = 0; j < nr[1]; ++j)
+            for (int i = 0; i < nr[0]; ++i) {
+              IBox b;
+              b.lo[0] = rlo[0][i];
+              b.hi[0] = rhi[0][i];
+              b.lo[1] = rlo[1][j];
+              b.hi[1] = rhi[1][j];
+              b.lo[2] = rlo[2][k];
+              b.hi[2] = rhi[2][k];
+              nest.push_back(b);
+            }
       }
     // the working lattice: the tag mask's region and the nesting cells
     const LevelTags &t = tags[l];

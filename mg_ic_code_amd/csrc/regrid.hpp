@@ -41,10 +41,14 @@ struct LevelTags {
 // BRMeshRefine::regrid stand-in, top-down: tags[0..top] -> boxes[1..top+1]
 // (out[l] = the boxes of level l + 1 in that level's cells; may be empty).
 // domain0: the level-0 domain box.  Returns 0 or -1 (err set); *new_finest =
-// the highest level with boxes (0: none).
+// the highest level with boxes (0: none).  periodic (null: no direction):
+// in a direction with periodic[d] != 0 the nesting region of a box is not
+// clipped to the domain but wrapped round it; clustering runs
+// inside the domain either way, so no box crosses a face.
 int regrid_levels(const std::vector<LevelTags> &tags, const IBox &domain0, int block_factor,
                   int max_grid_size, double fill_ratio, int nesting_radius,
-                  std::vector<std::vector<IBox>> *out, int *new_finest, std::string *err);
+                  std::vector<std::vector<IBox>> *out, int *new_finest, std::string *err,
+                  const int *periodic = nullptr);
 
 // LoadBalance stand-in: box i of the (sorted) list goes to rank
 // floor(size * (prefix_i + cells_i / 2) / total)

@@ -16,6 +16,12 @@ The loop of SetGrids.cpp:61-138, on device where the work is O(cells):
         levels 1..topLevel rebuilt, LoadBalance            :123-132
     until topLevel == max_level or topLevel did not grow   :135-136
 
+With periodic_regrid (the keyword, or the deck's regrid_periodic = 1) on a
+base with a periodic direction the tags and the proper nesting go through the
+wrap: the tag kernel is libmgic_ptag.so's k_ptag_lattice (one
+launch per level) and the nesting mgic_regrid_levels_periodic's.  This departs
+from the reference's local_tags &= domainBox (:201-202) on purpose.
+
 Chombo's BRMeshRefine is not part of the reference tree; the clustering is
 the Berger-Rigoutsos algorithm DESIGN.md 3f writes out, restated and not
 pinned against Chombo's box lists.  The base level stays the caller's grid
@@ -28,6 +34,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import _lib
 from ._lib import call
 from .core import BH_KEYS, Box6, Grid, LevelData, _ints, gloo_allgather
 from .matter import (FilledMatter, MatterArgumentError, PiProfile, resolve_matter,
@@ -68,6 +75,47 @@ def tag_lattice(cond: LevelData, tag_val: float, grow: int, c: int):
     return tuple(lo), mask
 
 
+def tag_lattice_periodic(cond: LevelData, tag_val: float, grow: int, c: int):
+    """tag_lattice through the wrap of the periodic directions of cond's grid
+    (libmgic_ptag.so, one launch for every local box): in such a direction the
+    lattice spans the domain and a tag's grown range is wrapped round it, not
+    clipped.  Returns (lat_lo, mask) as tag_lattice does."""
+    lo, n = (ctypes.c_int * 3)(), (ctypes.c_int * 3)()
+    comm = cond.grid.comm.handle
+    _lib.ptag_call("mgic_ptag_lattice", comm, cond.handle, ctypes.c_double(tag_val), int(grow),
+                   int(c), lo, n, None)
+    mask = np.zeros((n[2], n[1], n[0]), dtype=np.uint8)
+    _lib.ptag_call("mgic_ptag_lattice", comm, cond.handle, ctypes.c_double(tag_val), int(grow),
+                   int(c), lo, n, mask.ctypes.data_as(ctypes.c_void_p))
+    return tuple(lo), mask
+
+
+def ptag_launch_ledger() -> dict:
+    """{kernel: launches so far in this process} of libmgic_ptag.so."""
+    import os
+    import tempfile
+
+    from .core import read_launch_ledger
+    fd, path = tempfile.mkstemp(prefix="mgic_ptag_ledger_")
+    os.close(fd)
+    try:
+        _lib.ptag_call("mgic_ptag_launch_ledger_dump", path.encode())
+        return read_launch_ledger(path)
+    finally:
+        os.unlink(path)
+
+
+def resolve_periodic_regrid(periodic_regrid, prm) -> bool:
+    """set_grids' periodic_regrid: None -- the deck's regrid_periodic (absent:
+    0); True / False / 1 / 0; anything else is a ValueError."""
+    if periodic_regrid is None:
+        periodic_regrid = getattr(prm, "regrid_periodic", 0)
+    if isinstance(periodic_regrid, bool) or (isinstance(periodic_regrid, int) and
+                                             periodic_regrid in (0, 1)):
+        return bool(periodic_regrid)
+    raise ValueError(f"regrid_periodic must be 0 or 1 (False or True), got {periodic_regrid!r}")
+
+
 def _boxes_out(flat, n: int) -> List[Box6]:
     return [tuple(int(v) for v in flat[6 * i:6 * i + 6]) for i in range(n)]
 
@@ -91,9 +139,13 @@ def regrid_cluster(mask: np.ndarray, fill_ratio: float, maxlen: int) -> List[Box
 
 def regrid_levels(domain0: Box6, tags: Sequence[Tuple[Sequence[int], np.ndarray]],
                   block_factor: int, max_grid_size: int, fill_ratio: float,
-                  nesting_radius: int = NESTING_RADIUS) -> Tuple[List[List[Box6]], int]:
+                  nesting_radius: int = NESTING_RADIUS,
+                  periodic: Optional[Sequence[int]] = None) -> Tuple[List[List[Box6]], int]:
     """BRMeshRefine::regrid stand-in: tags[l] = (lat_lo, mask) of levels
-    0..top -> ([boxes of level 1, ..., boxes of level top + 1], new_finest)."""
+    0..top -> ([boxes of level 1, ..., boxes of level top + 1], new_finest).
+    periodic: None -- nesting regions are clipped to the domain
+    (mgic_regrid_levels); else three flags, and in a flagged direction they are
+    wrapped round it (mgic_regrid_levels_periodic)."""
     nlev = len(tags)
     masks = [np.ascontiguousarray(m, dtype=np.uint8) for _, m in tags]
     ptrs = (ctypes.c_void_p * nlev)(*[m.ctypes.data if m.size else None for m in masks])
@@ -101,12 +153,19 @@ def regrid_levels(domain0: Box6, tags: Sequence[Tuple[Sequence[int], np.ndarray]
     n = _ints([v for m in masks for v in m.shape[::-1]])
     nb = (ctypes.c_int * nlev)()
     fin = ctypes.c_int()
-    args = (nlev, _ints(domain0), ptrs, lo, n, int(block_factor), int(max_grid_size),
-            ctypes.c_double(fill_ratio), int(nesting_radius))
-    call("mgic_regrid_levels", *args, 0, nb, None, ctypes.byref(fin))
+    tail = (ptrs, lo, n, int(block_factor), int(max_grid_size), ctypes.c_double(fill_ratio),
+            int(nesting_radius))
+    if periodic is None:
+        name, args = "mgic_regrid_levels", (nlev, _ints(domain0)) + tail
+    else:
+        if len(periodic) != 3:
+            raise ValueError("periodic must be three flags")
+        name = "mgic_regrid_levels_periodic"
+        args = (nlev, _ints(domain0), _ints([1 if v else 0 for v in periodic])) + tail
+    call(name, *args, 0, nb, None, ctypes.byref(fin))
     total = sum(nb)
     out = (ctypes.c_int * (6 * max(total, 1)))()
-    call("mgic_regrid_levels", *args, total, nb, out, ctypes.byref(fin))
+    call(name, *args, total, nb, out, ctypes.byref(fin))
     boxes, at = [], 0
     for l in range(nlev):
         boxes.append(_boxes_out(out[6 * at:6 * (at + nb[l])], nb[l]))
@@ -134,7 +193,7 @@ def _level_max_norm(cond: LevelData) -> float:
 
 def set_grids(comm, prm: PoissonParameters, base_grid: Grid, max_level: Optional[int] = None,
               allgather=None, phi0: Optional[PhiProfile] = None, punctures=None,
-              matter=None) -> List[Grid]:
+              matter=None, periodic_regrid=None) -> List[Grid]:
     """The hierarchy set_grids generates over `base_grid` (level 0, covering
     the domain): [base_grid, Grid(patches=True) of level 1, ...], at most
     max_level (default prm.max_level) levels above the base.  comm.size > 1:
@@ -149,7 +208,16 @@ def set_grids(comm, prm: PoissonParameters, base_grid: Grid, max_level: Optional
     matter: None -- the deck's (prm.matter) if it has one, else no matter; else
     a matter.Matter whose pi is None or a PiProfile (levels appear and must be
     filled, so pre-filled fields cannot be taken): rho enters the regrid
-    condition through 1.5 |m|."""
+    condition through 1.5 |m|.
+    periodic_regrid: True -- on a base with a periodic direction the tags and
+    the proper nesting go through the wrap, so the hierarchy is
+    one AMRSolver accepts on that base; on a base with no periodic direction it
+    changes nothing and loads nothing.  None: the deck's regrid_periodic (0
+    when absent); anything but True / False / 1 / 0 is a ValueError.  With
+    more than one rank the lattice is the same on every rank (a periodic
+    direction spans the domain), so the OR over the ranks is unchanged; that
+    path is untested."""
+    wrap = resolve_periodic_regrid(periodic_regrid, prm) and any(base_grid.periodic)
     if phi0 is not None and not isinstance(phi0, PhiProfile):
         raise PhiArgumentError("set_grids", "phi0 must be a PhiProfile (levels appear and must "
                                f"be filled), not {type(phi0).__name__}")
@@ -186,14 +254,18 @@ def set_grids(comm, prm: PoissonParameters, base_grid: Grid, max_level: Optional
             else:
                 set_regrid_condition_phi(None, phi0.fill(g, bh), cond, bh)
             tag_val = _level_max_norm(cond) * prm.refine_threshold
-            lat_lo, mask = tag_lattice(cond, tag_val, TAGS_GROW, c)
+            if wrap:
+                lat_lo, mask = tag_lattice_periodic(cond, tag_val, TAGS_GROW, c)
+            else:
+                lat_lo, mask = tag_lattice(cond, tag_val, TAGS_GROW, c)
             if comm.size > 1:
                 parts = allgather(mask.tobytes())
                 for p in parts:
                     mask |= np.frombuffer(p, dtype=np.uint8).reshape(mask.shape)
             tags.append((lat_lo, mask))
         boxes, new_finest = regrid_levels(base_grid.domain, tags, prm.block_factor,
-                                          prm.max_grid_size, prm.fill_ratio)
+                                          prm.max_grid_size, prm.fill_ratio,
+                                          periodic=base_grid.periodic if wrap else None)
         if new_finest > top:
             top += 1
         elif new_finest < top:

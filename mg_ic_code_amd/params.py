@@ -86,6 +86,10 @@ class PoissonParameters:
     # 3l), which makes the composite operator conservative; absent: 0.  It has
     # no effect on one level
     reflux: int = 0
+    # regrid_periodic = 0|1 (not a key of the reference): 1 takes set_grids'
+    # tags and proper nesting through the wrap of a periodic base (DESIGN.md
+    # 3m); absent: 0.  It has no effect on a base that is not periodic
+    regrid_periodic: int = 0
 
     # what getPoissonParameters derives besides (PoissonParameters.cpp:68, :78-79,
     # :111-128): one more level than max_level, ratio 2 on every level, the
@@ -212,6 +216,11 @@ def read_params(text: str, overrides: Optional[Dict[str, str]] = None) -> Poisso
         if rf not in (0, 1):
             raise ValueError(f"reflux must be 0 or 1, got {rf}")
         p.reflux = rf
+    rp = get("regrid_periodic", int, required=False)
+    if rp is not None:
+        if rp not in (0, 1):
+            raise ValueError(f"regrid_periodic must be 0 or 1, got {rp}")
+        p.regrid_periodic = rp
     return p
 
 

@@ -7,7 +7,12 @@ ms per call over `reps` calls.  The tag call's time includes its mask clear,
 the device-to-host copy of the lattice mask and the synchronise; the kernel's
 own time comes from a kernel trace of this program (k_tag_lattice).
 
+With --periodic-ab the base is periodic in every direction and set_grids is
+timed with periodic_regrid off, on and off again in this one process (DESIGN.md
+3m); the kernel's own time comes from a kernel trace (k_ptag_lattice).
+
 usage: python tools/bench_regrid.py [params.txt] [--size N] [--max-level K] [--reps R]
+                                    [--periodic-ab]
 """
 import argparse
 import json
@@ -25,6 +30,8 @@ def main():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--max-level", type=int, default=2)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--periodic-ab", action="store_true",
+                    help="a periodic base: set_grids with periodic_regrid off, on, off")
     args = ap.parse_args()
     import mg_ic_code_amd as mg
     from mg_ic_code_amd import grids as G
@@ -35,6 +42,23 @@ def main():
     dom = (0, 0, 0, n - 1, n - 1, n - 1)
     base = mg.Grid(comm, dom, [dom], prm.domainLength[0] / n)
     res = {"size": n, "max_level": args.max_level}
+    if args.periodic_ab:
+        pbase = mg.Grid(comm, dom, [dom], prm.domainLength[0] / n, periodic=(1, 1, 1))
+        res["periodic_ab"] = []
+        for on in (False, True, False):
+            G.set_grids(comm, prm, pbase, max_level=args.max_level, periodic_regrid=on)  # warm-up
+            comm.synchronize()
+            t = []
+            for _ in range(args.reps):
+                t0 = time.perf_counter()
+                g = G.set_grids(comm, prm, pbase, max_level=args.max_level, periodic_regrid=on)
+                comm.synchronize()
+                t.append(time.perf_counter() - t0)
+            res["periodic_ab"].append({"periodic_regrid": on, "boxes": [len(x.boxes) for x in g],
+                                       "set_grids_ms": {"min": round(min(t) * 1e3, 2),
+                                                        "max": round(max(t) * 1e3, 2)}})
+        print(json.dumps(res), flush=True)
+        return
 
     def set_grids():
         g = G.set_grids(comm, prm, base, max_level=args.max_level)

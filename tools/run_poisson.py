@@ -41,9 +41,14 @@ With --reflux (or the deck's reflux = 1) every multi-level operator of the
 solve adds the reflux term at the coarse-fine faces: the
 composite operator is conservative, and a periodic hierarchy takes
 --momentum-zero-mode project.  --level-boxes gives the boxes of one finer
-level explicitly (repeat it per level) instead of --max-level's tagging: a
-periodic hierarchy has to be nested through the wrap, which the tagging does
-not see to.  The levels take the deck's is_periodic, as the base does.
+level explicitly (repeat it per level) instead of --max-level's tagging.  The
+levels take the deck's is_periodic, as the base does.
+
+With --regrid-periodic (or the deck's regrid_periodic = 1) --max-level's
+tagging and proper nesting go through the wrap of a periodic base (DESIGN.md
+3m): a periodic hierarchy has to be nested through the wrap, which the
+tagging does not see to without it.  It has no effect on a base that is not
+periodic.
 
 usage: python tools/run_poisson.py [params.txt] [--size N] [--boxes-per-rank x,y,z]
                                    [--max-level K] [--phi gaussian|sine]
@@ -52,6 +57,7 @@ usage: python tools/run_poisson.py [params.txt] [--size N] [--boxes-per-rank x,y
                                    [--constraints] [--momentum]
                                    [--momentum-zero-mode refuse|project] [--reflux]
                                    [--level-boxes "lo0 lo1 lo2 hi0 hi1 hi2; ..."]...
+                                   [--regrid-periodic]
 """
 import argparse
 import json
@@ -93,6 +99,9 @@ def main():
                     help="the boxes of the next finer level, \"lo0 lo1 lo2 hi0 hi1 hi2; ...\" in "
                          "that level's index space; repeatable, coarsest first; instead of "
                          "--max-level")
+    ap.add_argument("--regrid-periodic", action="store_true",
+                    help="--max-level's tags and nesting go through the wrap of a periodic base "
+                         "(default: the deck's regrid_periodic)")
     args = ap.parse_args()
     import mg_ic_code_amd as mg
     from mg_ic_code_amd.decomposition import decompose
@@ -130,7 +139,8 @@ def main():
     if args.max_level > 0:
         from mg_ic_code_amd.grids import set_grids
         levels = set_grids(grid.comm, prm, grid, max_level=args.max_level, phi0=phi0,
-                           punctures=punct, matter=matter)
+                           punctures=punct, matter=matter,
+                           periodic_regrid=True if args.regrid_periodic else None)
         for lev, g in enumerate(levels):
             cells = sum((b[3] - b[0] + 1) * (b[4] - b[1] + 1) * (b[5] - b[2] + 1) for b in g.boxes)
             print(f"level {lev}: {len(g.boxes)} boxes, {cells} cells")
