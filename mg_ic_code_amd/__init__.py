@@ -31,6 +31,7 @@ from .core import (  # noqa: F401
     set_nl_coefs,
     set_device,
 )
+from .adm import AdmReport, adm_charges, surface_terms  # noqa: F401
 from .constraints import (  # noqa: F401
     ConstraintFields,
     ConstraintReport,

@@ -568,6 +568,49 @@ def ptag_call(name: str, *args) -> int:
     return st
 
 
+# ---- libmgic_adm.so (include/mgic_adm.h): the surface-charge kernels (ADM
+# mass, momentum and spin on cubes of level 0), loaded on first use (adm.py);
+# missing or unloadable = an ImportError, no fallback
+ADM_LIB_PATH = os.path.join(_HERE, "libmgic_adm.so")
+ADM_SIGNATURES = {
+    "mgic_adm_last_error": [],
+    "mgic_adm_surface_count": [c_int, PI, PLL],
+    "mgic_adm_surface_terms": [H, H, c_int, PI, c_int, PD, PH, c_void_p, c_int],
+    "mgic_adm_charges": [H, H, c_int, PI, c_int, PD, PH, PD],
+    "mgic_adm_launch_ledger_dump": [c_char_p],
+    "mgic_adm_launch_ledger_reset": [],
+}
+_adm = None
+
+
+def adm_lib() -> ctypes.CDLL:
+    global _adm
+    if _adm is None:
+        if not os.path.exists(ADM_LIB_PATH):
+            raise ImportError(f"{ADM_LIB_PATH} not found: build it with __graft_entry__.build()")
+        L = ctypes.CDLL(ADM_LIB_PATH)
+        for name, argtypes in ADM_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.argtypes = argtypes
+            fn.restype = c_char_p if name == "mgic_adm_last_error" else c_int
+        _adm = L
+    return _adm
+
+
+def adm_loaded() -> bool:
+    """Whether libmgic_adm.so has been loaded by this process."""
+    return _adm is not None
+
+
+def adm_call(name: str, *args) -> int:
+    L = adm_lib()
+    st = getattr(L, name)(*args)
+    if st < 0:
+        msg = L.mgic_adm_last_error()
+        raise MgicError(name, st, msg.decode() if msg else "")
+    return st
+
+
 def last_error() -> str:
     msg = lib.mgic_last_error()
     return msg.decode() if msg else ""

@@ -51,6 +51,7 @@ import os
 from .core import (AMRMultiGrid, AMRSolver, BiCGStabSolver, Grid, LevelData, MultilevelLinearOp,
                    OperatorParams, SolverParams, defineOperatorFactory, set_nl_coefs, BH_KEYS)
 from ._lib import call
+from .adm import adm_charges, check_base, check_hierarchy, parse_half_widths
 from .constraints import constraints as constraint_report
 from .output import output_final_data, output_solver_data
 from .matter import fill_matter, resolve_matter, set_nl_coefs_matter, set_nl_integrand_matter
@@ -99,6 +100,9 @@ class NLResult:
     # max norm of the BiCGStab, max|rhs| as it took it); (0.0, 0.0) where the
     # right-hand side was all zero
     momentum_residuals: List[List[tuple]] = field(default_factory=list)
+    # poisson_solve(adm=[n_R, ...]): the adm.AdmReport of the returned psi (and
+    # of the total tensor, with momentum=True)
+    adm: object = None
 
 
 def set_nl_integrand(psi: LevelData, out: LevelData, bh: dict) -> None:
@@ -144,7 +148,7 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
                   output_dir: Optional[str] = None, phi0=None, punctures=None,
                   matter=None, constraints: bool = False,
                   momentum: Optional[bool] = None,
-                  zero_mode: Optional[str] = None, reflux=None) -> NLResult:
+                  zero_mode: Optional[str] = None, reflux=None, adm=None) -> NLResult:
     """phi0: None -- the analytic Gaussian, evaluated in the kernels; else a
     phi.PhiProfile, or one pre-filled LevelData per level: phi_0 is stored once
     before the NL loop (set_initial_conditions, SetLevelData.cpp:32-71) and the
@@ -182,7 +186,23 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
     coarse-fine faces, and the projection of the momentum solve
     on a periodic hierarchy is the composite one (momentum.py); on one level
     it changes nothing and loads nothing.  None: the deck's reflux (0 when
-    absent); anything but True / False / 1 / 0 is a ValueError."""
+    absent); anything but True / False / 1 / 0 is a ValueError.
+    adm: half-widths [n_R, ...] in level-0 cells -- the ADM mass, momentum and
+    spin of the returned psi on those cubes (adm.py; of the total tensor with
+    momentum=True) are attached as NLResult.adm.  The solve itself and the
+    output files are unchanged.  A periodic base, and any surface adm_charges
+    would refuse, is a ValueError before anything is stored or launched.
+    None: the deck's adm_half_widths; absent there too: nothing of it is
+    loaded or launched."""
+    if adm is None:
+        adm = getattr(prm, "adm_half_widths", None)
+    if adm is not None:  # refused before anything is stored or launched
+        adm = parse_half_widths(adm, "poisson_solve")
+        glist = list(grid) if isinstance(grid, (list, tuple)) else [grid]
+        if prm.is_periodic:
+            raise ValueError("adm: the charges are not defined on a periodic domain")
+        check_base(glist[0].domain, glist[0].periodic, adm, "poisson_solve")
+        check_hierarchy(glist, adm, "poisson_solve")
     punct = resolve_punctures(punctures, prm)
     zero_mode = resolve_zero_mode(zero_mode, prm)
     reflux = resolve_reflux(reflux, prm)
@@ -196,7 +216,7 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
         if len(grid) > 1:
             return _poisson_solve_amr(list(grid), prm, max_depth, prolong_type, bottom_solver,
                                       max_NL_iterations, output_dir, phi0, punct, matter,
-                                      constraints, momentum, zero_mode, reflux)
+                                      constraints, momentum, zero_mode, reflux, adm)
         grid = grid[0]
     mat = fill_matter(matter, [grid], prm)
     phis = resolve_phi0(phi0, [grid], prm)
@@ -282,6 +302,8 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
         res.constraints = constraint_report(
             psi, bh, phis, punct, mat, momentum=mom,
             momentum_net=res.momentum_net[-1] if res.momentum_net else None)
+    if adm is not None:
+        res.adm = adm_charges(psi, prm, adm, punctures=punct, momentum=mom)
     return res
 
 
@@ -313,7 +335,7 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
                        output_dir: Optional[str], phi0=None, punct=None,
                        matter=None, constraints: bool = False,
                        momentum: bool = False, zero_mode: str = "refuse",
-                       reflux: bool = False) -> NLResult:
+                       reflux: bool = False, adm=None) -> NLResult:
     """poissonSolve over nlevels = len(grids) AMR levels (Main_PoissonSolver.cpp:51-250)."""
     periodic = bool(prm.is_periodic)
     if periodic != all(grids[0].periodic):
@@ -397,6 +419,8 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
         res.constraints = constraint_report(
             psi, bh, phis, punct, mat, momentum=mom,
             momentum_net=res.momentum_net[-1] if res.momentum_net else None, reflux=reflux)
+    if adm is not None:
+        res.adm = adm_charges(psi, prm, adm, punctures=punct, momentum=mom)
     return res
 
 

@@ -90,6 +90,11 @@ class PoissonParameters:
     # tags and proper nesting through the wrap of a periodic base (DESIGN.md
     # 3m); absent: 0.  It has no effect on a base that is not periodic
     regrid_periodic: int = 0
+    # adm_half_widths = n1 n2 ... (not a key of the reference): the half-widths,
+    # in level-0 cells, of the cubes on which the ADM mass, momentum and spin of
+    # the solved data are reported (adm.py); 1 to 8 integers;
+    # absent: None, nothing of it is loaded or launched
+    adm_half_widths: Optional[List[int]] = None
 
     # what getPoissonParameters derives besides (PoissonParameters.cpp:68, :78-79,
     # :111-128): one more level than max_level, ratio 2 on every level, the
@@ -221,6 +226,14 @@ def read_params(text: str, overrides: Optional[Dict[str, str]] = None) -> Poisso
         if rp not in (0, 1):
             raise ValueError(f"regrid_periodic must be 0 or 1, got {rp}")
         p.regrid_periodic = rp
+    if "adm_half_widths" in kv:
+        try:
+            hw = [int(x) for x in kv["adm_half_widths"]]
+        except ValueError:
+            raise ValueError(f"adm_half_widths must be integers, got {kv['adm_half_widths']}")
+        if not 1 <= len(hw) <= 8 or min(hw) < 1:
+            raise ValueError(f"adm_half_widths must be 1 to 8 integers >= 1, got {hw}")
+        p.adm_half_widths = hw
     return p
 
 

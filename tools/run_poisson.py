@@ -50,6 +50,11 @@ tagging and proper nesting go through the wrap of a periodic base (DESIGN.md
 tagging does not see to without it.  It has no effect on a base that is not
 periodic.
 
+With --adm "n1 n2 ..." (or the deck's adm_half_widths) the ADM mass, momentum
+and spin of the solved data (mg_ic_code_amd/adm.py) are reported
+after the loop on the cubes of those half-widths (level-0 cells): one line per
+surface, then the totals the puncture table asks for.  Not on a periodic deck.
+
 usage: python tools/run_poisson.py [params.txt] [--size N] [--boxes-per-rank x,y,z]
                                    [--max-level K] [--phi gaussian|sine]
                                    [--puncture "m x y z Px Py Pz Jx Jy Jz"]...
@@ -57,7 +62,7 @@ usage: python tools/run_poisson.py [params.txt] [--size N] [--boxes-per-rank x,y
                                    [--constraints] [--momentum]
                                    [--momentum-zero-mode refuse|project] [--reflux]
                                    [--level-boxes "lo0 lo1 lo2 hi0 hi1 hi2; ..."]...
-                                   [--regrid-periodic]
+                                   [--regrid-periodic] [--adm "n1 n2 ..."]
 """
 import argparse
 import json
@@ -102,6 +107,9 @@ def main():
     ap.add_argument("--regrid-periodic", action="store_true",
                     help="--max-level's tags and nesting go through the wrap of a periodic base "
                          "(default: the deck's regrid_periodic)")
+    ap.add_argument("--adm", default=None, metavar="\"N1 N2 ...\"",
+                    help="report the ADM mass, momentum and spin on the cubes of these "
+                         "half-widths in level-0 cells (default: the deck's adm_half_widths)")
     args = ap.parse_args()
     import mg_ic_code_amd as mg
     from mg_ic_code_amd.decomposition import decompose
@@ -162,7 +170,7 @@ def main():
                         matter=matter, constraints=args.constraints,
                         momentum=True if args.momentum else None,
                         zero_mode=args.momentum_zero_mode,
-                        reflux=True if args.reflux else None)
+                        reflux=True if args.reflux else None, adm=args.adm)
     mg.device_synchronize()
     dt = time.perf_counter() - t0
     for i, (nrm, it) in enumerate(zip(res.dpsi_norms, res.linear_iterations)):
@@ -175,6 +183,9 @@ def main():
                  if res.momentum_net else ""))
     if args.constraints:
         for line in res.constraints.lines():
+            print(line)
+    if res.adm is not None:
+        for line in res.adm.lines():
             print(line)
     out = {"n": n, "boxes": len(boxes), "nl_iterations": len(res.dpsi_norms),
            "converged": res.converged, "seconds": round(dt, 3)}
