@@ -52,5 +52,14 @@ from .momentum import (  # noqa: F401
 from .output import output_final_data, output_solver_data  # noqa: F401
 from .phi import PhiProfile  # noqa: F401
 from .punctures import Puncture, PunctureSet  # noqa: F401
+from .sample import (  # noqa: F401
+    MassSolveResult,
+    PunctureMassReport,
+    SampleResult,
+    lineout,
+    puncture_masses,
+    sample_points,
+    solve_for_masses,
+)
 
 __version__ = "0.1.0"

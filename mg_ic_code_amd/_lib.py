@@ -611,6 +611,48 @@ def adm_call(name: str, *args) -> int:
     return st
 
 
+# ---- libmgic_sample.so (include/mgic_sample.h): the point-sampling kernel (a
+# field of the hierarchy interpolated at points), loaded on first use
+# (sample.py); missing or unloadable = an ImportError, no fallback
+SAMPLE_LIB_PATH = os.path.join(_HERE, "libmgic_sample.so")
+SAMPLE_SIGNATURES = {
+    "mgic_sample_last_error": [],
+    "mgic_sample_points": [H, c_int, PH, c_int, PD, c_int, PD, PI, PI],
+    "mgic_sample_launch_ledger_dump": [c_char_p],
+    "mgic_sample_launch_ledger_reset": [],
+}
+_sample = None
+
+
+def sample_lib() -> ctypes.CDLL:
+    global _sample
+    if _sample is None:
+        if not os.path.exists(SAMPLE_LIB_PATH):
+            raise ImportError(
+                f"{SAMPLE_LIB_PATH} not found: build it with __graft_entry__.build()")
+        L = ctypes.CDLL(SAMPLE_LIB_PATH)
+        for name, argtypes in SAMPLE_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.argtypes = argtypes
+            fn.restype = c_char_p if name == "mgic_sample_last_error" else c_int
+        _sample = L
+    return _sample
+
+
+def sample_loaded() -> bool:
+    """Whether libmgic_sample.so has been loaded by this process."""
+    return _sample is not None
+
+
+def sample_call(name: str, *args) -> int:
+    L = sample_lib()
+    st = getattr(L, name)(*args)
+    if st < 0:
+        msg = L.mgic_sample_last_error()
+        raise MgicError(name, st, msg.decode() if msg else "")
+    return st
+
+
 def last_error() -> str:
     msg = lib.mgic_last_error()
     return msg.decode() if msg else ""

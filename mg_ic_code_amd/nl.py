@@ -51,7 +51,8 @@ import os
 from .core import (AMRMultiGrid, AMRSolver, BiCGStabSolver, Grid, LevelData, MultilevelLinearOp,
                    OperatorParams, SolverParams, defineOperatorFactory, set_nl_coefs, BH_KEYS)
 from ._lib import call
-from .adm import adm_charges, check_base, check_hierarchy, parse_half_widths
+from . import sample as _sample
+from .adm import adm_charges, check_base, check_hierarchy, parse_half_widths, resolve_table
 from .constraints import constraints as constraint_report
 from .output import output_final_data, output_solver_data
 from .matter import fill_matter, resolve_matter, set_nl_coefs_matter, set_nl_integrand_matter
@@ -103,6 +104,9 @@ class NLResult:
     # poisson_solve(adm=[n_R, ...]): the adm.AdmReport of the returned psi (and
     # of the total tensor, with momentum=True)
     adm: object = None
+    # poisson_solve(puncture_masses=True): the sample.PunctureMassReport of the
+    # returned psi (psi at every puncture and the ADM mass it gives)
+    puncture_masses: object = None
 
 
 def set_nl_integrand(psi: LevelData, out: LevelData, bh: dict) -> None:
@@ -148,7 +152,8 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
                   output_dir: Optional[str] = None, phi0=None, punctures=None,
                   matter=None, constraints: bool = False,
                   momentum: Optional[bool] = None,
-                  zero_mode: Optional[str] = None, reflux=None, adm=None) -> NLResult:
+                  zero_mode: Optional[str] = None, reflux=None, adm=None,
+                  puncture_masses: Optional[bool] = None) -> NLResult:
     """phi0: None -- the analytic Gaussian, evaluated in the kernels; else a
     phi.PhiProfile, or one pre-filled LevelData per level: phi_0 is stored once
     before the NL loop (set_initial_conditions, SetLevelData.cpp:32-71) and the
@@ -193,7 +198,18 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
     output files are unchanged.  A periodic base, and any surface adm_charges
     would refuse, is a ValueError before anything is stored or launched.
     None: the deck's adm_half_widths; absent there too: nothing of it is
-    loaded or launched."""
+    loaded or launched.
+    puncture_masses: True -- psi at every puncture of the table (the deck's two
+    holes as a table without one) and the ADM mass it gives (sample.py) are
+    attached as NLResult.puncture_masses, taken from the returned psi on the
+    finest level that holds each puncture.  The solve itself and the output
+    files are unchanged.  Two punctures at one position are a ValueError before
+    anything is stored or launched.  None: the deck's puncture_masses; absent
+    or 0 there: nothing of it is loaded or launched."""
+    if puncture_masses is None:
+        puncture_masses = bool(getattr(prm, "puncture_masses", 0))
+    if puncture_masses:  # refused before anything is stored or launched
+        _sample.check_distinct(resolve_table(punctures, prm), "poisson_solve")
     if adm is None:
         adm = getattr(prm, "adm_half_widths", None)
     if adm is not None:  # refused before anything is stored or launched
@@ -216,7 +232,8 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
         if len(grid) > 1:
             return _poisson_solve_amr(list(grid), prm, max_depth, prolong_type, bottom_solver,
                                       max_NL_iterations, output_dir, phi0, punct, matter,
-                                      constraints, momentum, zero_mode, reflux, adm)
+                                      constraints, momentum, zero_mode, reflux, adm,
+                                      bool(puncture_masses))
         grid = grid[0]
     mat = fill_matter(matter, [grid], prm)
     phis = resolve_phi0(phi0, [grid], prm)
@@ -304,6 +321,8 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
             momentum_net=res.momentum_net[-1] if res.momentum_net else None)
     if adm is not None:
         res.adm = adm_charges(psi, prm, adm, punctures=punct, momentum=mom)
+    if puncture_masses:
+        res.puncture_masses = _sample.puncture_masses(psi, prm, punctures=punct)
     return res
 
 
@@ -335,7 +354,8 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
                        output_dir: Optional[str], phi0=None, punct=None,
                        matter=None, constraints: bool = False,
                        momentum: bool = False, zero_mode: str = "refuse",
-                       reflux: bool = False, adm=None) -> NLResult:
+                       reflux: bool = False, adm=None,
+                       puncture_masses: bool = False) -> NLResult:
     """poissonSolve over nlevels = len(grids) AMR levels (Main_PoissonSolver.cpp:51-250)."""
     periodic = bool(prm.is_periodic)
     if periodic != all(grids[0].periodic):
@@ -421,6 +441,8 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
             momentum_net=res.momentum_net[-1] if res.momentum_net else None, reflux=reflux)
     if adm is not None:
         res.adm = adm_charges(psi, prm, adm, punctures=punct, momentum=mom)
+    if puncture_masses:
+        res.puncture_masses = _sample.puncture_masses(psi, prm, punctures=punct)
     return res
 
 

@@ -95,6 +95,15 @@ class PoissonParameters:
     # the solved data are reported (adm.py); 1 to 8 integers;
     # absent: None, nothing of it is loaded or launched
     adm_half_widths: Optional[List[int]] = None
+    # puncture_masses = 0|1 (not a key of the reference): 1 reports psi at every
+    # puncture and the ADM mass it gives (sample.py); absent: 0,
+    # nothing of it is loaded or launched
+    puncture_masses: int = 0
+    # target_masses = T1 T2 ... (not a key of the reference): the ADM masses the
+    # punctures are to have, one positive number per puncture in table order;
+    # tools/run_poisson.py then iterates the bare masses (sample.solve_for_masses);
+    # absent: None
+    target_masses: Optional[List[float]] = None
 
     # what getPoissonParameters derives besides (PoissonParameters.cpp:68, :78-79,
     # :111-128): one more level than max_level, ratio 2 on every level, the
@@ -234,6 +243,16 @@ def read_params(text: str, overrides: Optional[Dict[str, str]] = None) -> Poisso
         if not 1 <= len(hw) <= 8 or min(hw) < 1:
             raise ValueError(f"adm_half_widths must be 1 to 8 integers >= 1, got {hw}")
         p.adm_half_widths = hw
+    pm = get("puncture_masses", int, required=False)
+    if pm is not None:
+        if pm not in (0, 1):
+            raise ValueError(f"puncture_masses must be 0 or 1, got {pm}")
+        p.puncture_masses = pm
+    if "target_masses" in kv:
+        from .sample import check_target_count, parse_masses
+        tm = parse_masses(kv["target_masses"], "target_masses")  # a ValueError of its own
+        check_target_count(tm, len(p.punctures) if p.punctures is not None else 2, "target_masses")
+        p.target_masses = tm
     return p
 
 
