@@ -40,6 +40,14 @@ from .constraints import (  # noqa: F401
     set_constraints,
 )
 from .grids import set_grids  # noqa: F401
+from .horizon import (  # noqa: F401
+    ExpansionResult,
+    HorizonResult,
+    SurfaceBasis,
+    expansion_points,
+    find_horizon,
+    horizons_of,
+)
 from ._lib import CTT_LIB_PATH, IO_LIB_PATH, LIB_PATH, lib  # noqa: F401
 from .matter import Matter, PiProfile, ScalarPotential  # noqa: F401
 from .momentum import (  # noqa: F401

@@ -653,6 +653,48 @@ def sample_call(name: str, *args) -> int:
     return st
 
 
+# ---- libmgic_horizon.so (include/mgic_horizon.h): the expansion kernel (psi,
+# its gradient and Abar_ij n^i n^j at the points of a surface), loaded on first
+# use (horizon.py); missing or unloadable = an ImportError, no fallback
+HORIZON_LIB_PATH = os.path.join(_HERE, "libmgic_horizon.so")
+HORIZON_SIGNATURES = {
+    "mgic_horizon_last_error": [],
+    "mgic_horizon_expansion": [H, c_int, PH, PH, c_int, PD, c_int, PD, PD, PD, PD, PI, PI],
+    "mgic_horizon_launch_ledger_dump": [c_char_p],
+    "mgic_horizon_launch_ledger_reset": [],
+}
+_horizon = None
+
+
+def horizon_lib() -> ctypes.CDLL:
+    global _horizon
+    if _horizon is None:
+        if not os.path.exists(HORIZON_LIB_PATH):
+            raise ImportError(
+                f"{HORIZON_LIB_PATH} not found: build it with __graft_entry__.build()")
+        L = ctypes.CDLL(HORIZON_LIB_PATH)
+        for name, argtypes in HORIZON_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.argtypes = argtypes
+            fn.restype = c_char_p if name == "mgic_horizon_last_error" else c_int
+        _horizon = L
+    return _horizon
+
+
+def horizon_loaded() -> bool:
+    """Whether libmgic_horizon.so has been loaded by this process."""
+    return _horizon is not None
+
+
+def horizon_call(name: str, *args) -> int:
+    L = horizon_lib()
+    st = getattr(L, name)(*args)
+    if st < 0:
+        msg = L.mgic_horizon_last_error()
+        raise MgicError(name, st, msg.decode() if msg else "")
+    return st
+
+
 def last_error() -> str:
     msg = lib.mgic_last_error()
     return msg.decode() if msg else ""

@@ -51,6 +51,7 @@ import os
 from .core import (AMRMultiGrid, AMRSolver, BiCGStabSolver, Grid, LevelData, MultilevelLinearOp,
                    OperatorParams, SolverParams, defineOperatorFactory, set_nl_coefs, BH_KEYS)
 from ._lib import call
+from . import horizon as _horizon
 from . import sample as _sample
 from .adm import adm_charges, check_base, check_hierarchy, parse_half_widths, resolve_table
 from .constraints import constraints as constraint_report
@@ -107,6 +108,9 @@ class NLResult:
     # poisson_solve(puncture_masses=True): the sample.PunctureMassReport of the
     # returned psi (psi at every puncture and the ADM mass it gives)
     puncture_masses: object = None
+    # poisson_solve(horizons=...): one horizon.HorizonResult per requested
+    # surface, found on the returned psi (and the total tensor, with momentum=True)
+    horizons: object = None
 
 
 def set_nl_integrand(psi: LevelData, out: LevelData, bh: dict) -> None:
@@ -153,7 +157,7 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
                   matter=None, constraints: bool = False,
                   momentum: Optional[bool] = None,
                   zero_mode: Optional[str] = None, reflux=None, adm=None,
-                  puncture_masses: Optional[bool] = None) -> NLResult:
+                  puncture_masses: Optional[bool] = None, horizons=None) -> NLResult:
     """phi0: None -- the analytic Gaussian, evaluated in the kernels; else a
     phi.PhiProfile, or one pre-filled LevelData per level: phi_0 is stored once
     before the NL loop (set_initial_conditions, SetLevelData.cpp:32-71) and the
@@ -205,7 +209,22 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
     finest level that holds each puncture.  The solve itself and the output
     files are unchanged.  Two punctures at one position are a ValueError before
     anything is stored or launched.  None: the deck's puncture_masses; absent
-    or 0 there: nothing of it is loaded or launched."""
+    or 0 there: nothing of it is loaded or launched.
+    horizons: a list of (cx, cy, cz, r0), or "punctures" (one surface per
+    puncture of the table, centred on it, r0 = m_i) -- the apparent horizon
+    about each centre, from the sphere of radius r0 (horizon.py), is looked for
+    on the returned psi (and the total tensor, with momentum=True) and attached
+    as NLResult.horizons, one HorizonResult per surface, found or not.  The
+    solve itself and the output files are unchanged.  A periodic deck and a bad
+    centre or radius are a ValueError before anything is stored or launched.
+    None: the deck's horizons; absent there too: nothing of it is loaded or
+    launched."""
+    if horizons is None:
+        horizons = getattr(prm, "horizons", None)
+    if horizons is not None:  # refused before anything is stored or launched
+        _horizon.check_not_periodic(prm, "poisson_solve")
+        horizons = _horizon.resolve_horizons(horizons, resolve_table(punctures, prm),
+                                             "poisson_solve")
     if puncture_masses is None:
         puncture_masses = bool(getattr(prm, "puncture_masses", 0))
     if puncture_masses:  # refused before anything is stored or launched
@@ -233,7 +252,7 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
             return _poisson_solve_amr(list(grid), prm, max_depth, prolong_type, bottom_solver,
                                       max_NL_iterations, output_dir, phi0, punct, matter,
                                       constraints, momentum, zero_mode, reflux, adm,
-                                      bool(puncture_masses))
+                                      bool(puncture_masses), horizons)
         grid = grid[0]
     mat = fill_matter(matter, [grid], prm)
     phis = resolve_phi0(phi0, [grid], prm)
@@ -323,6 +342,8 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
         res.adm = adm_charges(psi, prm, adm, punctures=punct, momentum=mom)
     if puncture_masses:
         res.puncture_masses = _sample.puncture_masses(psi, prm, punctures=punct)
+    if horizons is not None:
+        res.horizons = _horizon.horizons_of(psi, prm, horizons, punctures=punct, momentum=mom)
     return res
 
 
@@ -355,7 +376,7 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
                        matter=None, constraints: bool = False,
                        momentum: bool = False, zero_mode: str = "refuse",
                        reflux: bool = False, adm=None,
-                       puncture_masses: bool = False) -> NLResult:
+                       puncture_masses: bool = False, horizons=None) -> NLResult:
     """poissonSolve over nlevels = len(grids) AMR levels (Main_PoissonSolver.cpp:51-250)."""
     periodic = bool(prm.is_periodic)
     if periodic != all(grids[0].periodic):
@@ -443,6 +464,8 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
         res.adm = adm_charges(psi, prm, adm, punctures=punct, momentum=mom)
     if puncture_masses:
         res.puncture_masses = _sample.puncture_masses(psi, prm, punctures=punct)
+    if horizons is not None:
+        res.horizons = _horizon.horizons_of(psi, prm, horizons, punctures=punct, momentum=mom)
     return res
 
 

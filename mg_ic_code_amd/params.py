@@ -104,6 +104,13 @@ class PoissonParameters:
     # tools/run_poisson.py then iterates the bare masses (sample.solve_for_masses);
     # absent: None
     target_masses: Optional[List[float]] = None
+    # num_horizons = n with horizon1 .. horizonN = cx cy cz r0, or horizons =
+    # punctures (not keys of the reference): the apparent horizon about each
+    # centre, from the sphere of radius r0, or about every puncture of the table
+    # from r0 = m_i, is looked for in the solved data (horizon.py, DESIGN.md
+    # 3p); a list of [cx, cy, cz, r0], or "punctures"; absent: None, nothing of
+    # it is loaded or launched
+    horizons: Optional[object] = None
 
     # what getPoissonParameters derives besides (PoissonParameters.cpp:68, :78-79,
     # :111-128): one more level than max_level, ratio 2 on every level, the
@@ -253,6 +260,27 @@ def read_params(text: str, overrides: Optional[Dict[str, str]] = None) -> Poisso
         tm = parse_masses(kv["target_masses"], "target_masses")  # a ValueError of its own
         check_target_count(tm, len(p.punctures) if p.punctures is not None else 2, "target_masses")
         p.target_masses = tm
+    nh = get("num_horizons", int, required=False)
+    if "horizons" in kv:
+        if kv["horizons"] != ["punctures"]:
+            raise ValueError(f"horizons must be punctures, got {' '.join(kv['horizons'])!r}")
+        if nh is not None:
+            raise ValueError("horizons = punctures and num_horizons exclude each other")
+        p.horizons = "punctures"
+    elif nh is not None:
+        from .horizon import parse_horizon
+        if nh < 1:
+            raise ValueError(f"num_horizons must be at least 1, got {nh}")
+        rows = []
+        for i in range(1, nh + 1):
+            key = f"horizon{i}"
+            if key not in kv:
+                raise KeyError(f"ParmParse::get: key '{key}' not found")
+            c, r0 = parse_horizon(kv[key], key)  # a ValueError of its own
+            rows.append([c[0], c[1], c[2], r0])
+        p.horizons = rows
+    if p.horizons is not None and p.is_periodic:
+        raise ValueError("horizons are not defined on a periodic domain (is_periodic = 1)")
     return p
 
 

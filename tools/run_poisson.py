@@ -69,6 +69,14 @@ With --lineout "x0 y0 z0 x1 y1 z1 n" the solved psi is sampled at n points
 from (x0, y0, z0) to (x1, y1, z1), both included: "lineout s value level order"
 per point, s the arc length.
 
+With --horizon "cx cy cz r0" (repeatable; or the deck's num_horizons, horizon1
+...) the apparent horizon about (cx, cy, cz) is looked for in the solved data
+from the sphere of radius r0 (mg_ic_code_amd/horizon.py, DESIGN.md 3p);
+--horizons-at-punctures (or the deck's horizons = punctures) looks about every
+puncture of the table from r0 = m_i.  Per surface: its status, and when found
+its radii, area, irreducible mass and the punctures it encloses; with
+--puncture-masses also M_irr next to M_i.  Not on a periodic deck.
+
 usage: python tools/run_poisson.py [params.txt] [--size N] [--boxes-per-rank x,y,z]
                                    [--max-level K] [--phi gaussian|sine]
                                    [--puncture "m x y z Px Py Pz Jx Jy Jz"]...
@@ -79,6 +87,7 @@ usage: python tools/run_poisson.py [params.txt] [--size N] [--boxes-per-rank x,y
                                    [--regrid-periodic] [--adm "n1 n2 ..."]
                                    [--puncture-masses] [--target-masses "T1 T2 ..."]
                                    [--lineout "x0 y0 z0 x1 y1 z1 n"]
+                                   [--horizon "cx cy cz r0"]... [--horizons-at-punctures]
 """
 import argparse
 import json
@@ -134,7 +143,14 @@ def main():
                          "(default: the deck's target_masses); implies --puncture-masses")
     ap.add_argument("--lineout", default=None, metavar="\"X0 Y0 Z0 X1 Y1 Z1 N\"",
                     help="sample the solved psi at N points from (X0, Y0, Z0) to (X1, Y1, Z1)")
+    ap.add_argument("--horizon", action="append", default=None, metavar="\"CX CY CZ R0\"",
+                    help="look for the apparent horizon about (CX, CY, CZ) from the sphere of "
+                         "radius R0; repeatable; overrides the deck's")
+    ap.add_argument("--horizons-at-punctures", action="store_true",
+                    help="look for a horizon about every puncture, from r0 = its bare mass")
     args = ap.parse_args()
+    if args.horizon and args.horizons_at_punctures:
+        ap.error("--horizon and --horizons-at-punctures exclude each other")
     import mg_ic_code_amd as mg
     from mg_ic_code_amd.decomposition import decompose
     from mg_ic_code_amd.nl import poisson_solve
@@ -195,7 +211,8 @@ def main():
     kwargs = dict(max_depth=args.max_depth, phi0=phi0, matter=matter,
                   constraints=args.constraints, momentum=True if args.momentum else None,
                   zero_mode=args.momentum_zero_mode, reflux=True if args.reflux else None,
-                  adm=args.adm)
+                  adm=args.adm,
+                  horizons="punctures" if args.horizons_at_punctures else args.horizon)
     t0 = time.perf_counter()
     msolve = None
     if targets is not None:
@@ -226,6 +243,10 @@ def main():
     if res.puncture_masses is not None:
         for text in res.puncture_masses.lines():
             print(text)
+    if res.horizons is not None:
+        from mg_ic_code_amd.horizon import horizon_lines
+        for text in horizon_lines(res.horizons, res.puncture_masses):
+            print(text)
     if lineout_spec is not None:
         for text in sample.lineout(res.psi, *lineout_spec).lines():
             print(text)
@@ -235,6 +256,8 @@ def main():
         out["punctures"] = [list(p.row()) for p in punct]
     if res.puncture_masses is not None:
         out["puncture_masses"] = res.puncture_masses.adm_masses
+    if res.horizons is not None:
+        out["horizons"] = [h.summary() for h in res.horizons]
     if msolve is not None:
         out["mass_solves"] = len(msolve.history)
         out["mass_solve_converged"] = msolve.converged
