@@ -132,6 +132,24 @@ MGIC_IO_API int mgic_io_write_final_data_ctt(const char *filename, int nlevels,
                                              const mgic_field *abar, int constraints,
                                              int max_level, const int *ref_ratio);
 
+/* The final-data writer of the CTTK method (mgic_cttk.h): K is
+ * a stored field, K[l] on psi[l]'s layout.  The file is what
+ * mgic_io_write_final_data_ctt writes at constant_K = 0 (bh[12] is ignored)
+ * with component 7, "K", copied from K[l]'s valid cells.  cons NULL:
+ * components 27-30 are zeros; else cons holds five fields per level, level
+ * l's at cons[5 l .. 5 l + 4] in the order Ham, Mom1, Mom2, Mom3, Ham_abs
+ * (the corrected fields of mgic_cttk_constraints), and components 27-30 are
+ * copied from the first four.  Host code: the stored fields come through
+ * mgic_field_download.  What the _ctt form refuses, and a NULL K or cons field
+ * or one of another layout, are MGIC_EBADARG before the file is created. */
+MGIC_IO_API int mgic_io_write_final_data_cttk(const char *filename, int nlevels,
+                                              const mgic_field *psi, const mgic_field *phi,
+                                              const double bh[13], int npunct,
+                                              const double *table, const mgic_field *pi,
+                                              const double pot[3], const mgic_field *abar,
+                                              const mgic_field *K, const mgic_field *cons,
+                                              int max_level, const int *ref_ratio);
+
 /* The same two layouts from host arrays (tests, and callers whose data is
  * already on the host).  kind 0: final data (31 components), 1: solver data
  * (10).  Level l has nbox[l] boxes (6 ints each, all levels concatenated in

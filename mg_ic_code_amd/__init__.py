@@ -39,6 +39,7 @@ from .constraints import (  # noqa: F401
     constraints,
     set_constraints,
 )
+from .cttk import CTTKError, CTTKResult, cttk_solve  # noqa: F401
 from .grids import set_grids  # noqa: F401
 from .horizon import (  # noqa: F401
     ExpansionResult,

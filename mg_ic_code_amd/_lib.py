@@ -367,6 +367,8 @@ IO_SIGNATURES = {
                                              PI],
     "mgic_io_write_final_data_ctt": [c_char_p, c_int, PH, PH, PD, c_int, PD, PH, PD, PH, c_int,
                                      c_int, PI],
+    "mgic_io_write_final_data_cttk": [c_char_p, c_int, PH, PH, PD, c_int, PD, PH, PD, PH, PH, PH,
+                                      c_int, PI],
     "mgic_io_write_host": [c_char_p, c_int, c_int, PI, PI, PI, PD, PI, PD, c_int, c_int],
 }
 _io = None
@@ -691,6 +693,49 @@ def horizon_call(name: str, *args) -> int:
     st = getattr(L, name)(*args)
     if st < 0:
         msg = L.mgic_horizon_last_error()
+        raise MgicError(name, st, msg.decode() if msg else "")
+    return st
+
+
+# ---- libmgic_cttk.so (include/mgic_cttk.h): the K(x) kernels of the CTTK
+# method, loaded on first use (cttk.py); missing or unloadable = an
+# ImportError, no fallback
+CTTK_LIB_PATH = os.path.join(_HERE, "libmgic_cttk.so")
+CTTK_SIGNATURES = {
+    "mgic_cttk_last_error": [],
+    "mgic_cttk_K": [H, H, H, PLL],
+    "mgic_cttk_source": [H, H, H, PH],
+    "mgic_cttk_constraints": [H, H, H, PH, H],
+    "mgic_cttk_launch_ledger_dump": [c_char_p],
+    "mgic_cttk_launch_ledger_reset": [],
+}
+_cttk = None
+
+
+def cttk_lib() -> ctypes.CDLL:
+    global _cttk
+    if _cttk is None:
+        if not os.path.exists(CTTK_LIB_PATH):
+            raise ImportError(f"{CTTK_LIB_PATH} not found: build it with __graft_entry__.build()")
+        L = ctypes.CDLL(CTTK_LIB_PATH)
+        for name, argtypes in CTTK_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.argtypes = argtypes
+            fn.restype = c_char_p if name == "mgic_cttk_last_error" else c_int
+        _cttk = L
+    return _cttk
+
+
+def cttk_loaded() -> bool:
+    """Whether libmgic_cttk.so has been loaded by this process."""
+    return _cttk is not None
+
+
+def cttk_call(name: str, *args) -> int:
+    L = cttk_lib()
+    st = getattr(L, name)(*args)
+    if st < 0:
+        msg = L.mgic_cttk_last_error()
         raise MgicError(name, st, msg.decode() if msg else "")
     return st
 

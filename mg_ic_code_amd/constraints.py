@@ -185,7 +185,7 @@ def _field_norm(x: LevelData, ord: int) -> float:
 
 def constraints(psi, prm, phi0=None, punctures=None, matter=None,
                 constant_K: Optional[float] = None, momentum=None,
-                momentum_net=None, reflux: bool = False) -> ConstraintReport:
+                momentum_net=None, reflux: bool = False, correct=None) -> ConstraintReport:
     """The constraints of the data at psi (a LevelData, or one per AMR level,
     coarsest first) and their norms.
 
@@ -203,7 +203,10 @@ def constraints(psi, prm, phi0=None, punctures=None, matter=None,
     report also carries the norms of Mom_i + m_i psi_0^-6, the offset added
     cell by cell on every level.  reflux: the geometry-only AMRSolver of a
     hierarchy's norms is built with it, as the solve's are (the norms do not
-    depend on it).
+    depend on it).  correct: None, or a callable (level, ConstraintFields)
+    run on every level's five fields before any norm is taken (cttk.py: the
+    terms of a K that varies in space, on top of the fields at constant_K =
+    0).
 
     On one level the norms are the operator's norm(x, 0) and norm(x, 2) *
     dx^1.5; over a hierarchy AMRSolver.computeNorm, so covered coarse cells
@@ -229,6 +232,8 @@ def constraints(psi, prm, phi0=None, punctures=None, matter=None,
                         mat.level(l) if mat is not None else None, punct,
                         phis[l] if phis is not None else None,
                         momentum.lw(l) if momentum is not None else None)
+        if correct is not None:
+            correct(l, rep.fields[l])
     if len(grids) == 1:
         dx = grids[0].dx
         fs = rep.fields[0].fields()

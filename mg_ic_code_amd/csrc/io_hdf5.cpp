@@ -630,6 +630,86 @@ MGIC_IO_API int mgic_io_write_final_data_ctt(const char *filename, int nlevels,
                           pot, constraints != 0, abar);
 }
 
+// the _ctt form's checks with K (and the five constraint fields) of every
+// level; the slabs are the _ctt form's at bh[12] = 0 with component 7 copied
+// from K and, with cons, components 27-30 from cons[5 l .. 5 l + 3]
+MGIC_IO_API int mgic_io_write_final_data_cttk(const char *filename, int nlevels,
+                                              const mgic_field *psi, const mgic_field *phi,
+                                              const double bh[13], int npunct,
+                                              const double *table, const mgic_field *pi,
+                                              const double pot[3], const mgic_field *abar,
+                                              const mgic_field *K, const mgic_field *cons,
+                                              int max_level, const int *ref_ratio) {
+  const int st = guard([&] {
+    if (table || npunct != 0) check_punctures(npunct, table);
+    need(pot, "pot");
+    for (int c = 0; c < 3; ++c)
+      if (!std::isfinite(pot[c]))
+        throw IoError(MGIC_EBADARG, "potential coefficients (V0, mass, lambda) must be finite");
+    need(psi, "psi");
+    need(bh, "bh");
+    need(abar, "abar");
+    need(K, "K");
+    need(ref_ratio, "ref_ratio");
+    if (nlevels < 1) throw IoError(MGIC_EBADARG, "nlevels < 1");
+    for (int l = 0; l < nlevels; ++l) {
+      need(psi[l], "psi[l]");
+      if (phi) need(phi[l], "phi[l]");
+      if (pi) {
+        need(pi[l], "pi[l]");
+        check_pi_layout(psi[l], pi[l]);
+      }
+      for (int c = 0; c < 6; ++c) {
+        need(abar[6 * l + c], "abar[6 l + c]");
+        check_pi_layout(psi[l], abar[6 * l + c]);
+      }
+      need(K[l], "K[l]");
+      check_pi_layout(psi[l], K[l]);
+      for (int c = 0; cons && c < 5; ++c) {
+        need(cons[5 * l + c], "cons[5 l + c]");
+        check_pi_layout(psi[l], cons[5 * l + c]);
+      }
+    }
+  });
+  if (st != MGIC_OK) return st;
+  return guard([&] {
+    double bh0[13];
+    std::copy(bh, bh + 13, bh0);
+    bh0[12] = 0.0;  // constant_K: K is the field's
+    Job J;
+    J.kind = 0;
+    J.ncomp = 31;
+    J.max_level = max_level;
+    J.ref_ratio.assign(ref_ratio, ref_ratio + nlevels);
+    std::vector<mgic_field> lead(psi, psi + nlevels);
+    std::vector<double> box;  // one stored field over the valid cells of a box
+    auto copy_in = [&](mgic_field f, int n, int k0, int nk, long long plane, double *dst) {
+      int dom[6], per[3], nbox = 0, rank = 0, size = 1;
+      double dx = 0.0;
+      mg(mgic_field_layout(f, dom, per, &dx, &nbox, &rank, &size));
+      long long nz = 0;
+      for (int b = 0; b < nbox && !nz; ++b) {
+        int lohi[6], owner = 0, loc = -1;
+        mg(mgic_field_box(f, b, lohi, &owner, &loc));
+        if (loc == n) nz = lohi[5] - lohi[2] + 1;
+      }
+      if (k0 < 0 || nk < 0 || k0 + nk > nz) throw IoError(MGIC_EUNKNOWN, "slab outside its box");
+      box.resize((size_t)(plane * nz));
+      mg(mgic_field_download(f, n, box.data(), 0));
+      std::copy(box.begin() + (size_t)(plane * k0), box.begin() + (size_t)(plane * (k0 + nk)), dst);
+    };
+    write_fields(filename ? filename : "vcPoissonFinal.3d.hdf5", J, lead,
+                 [&](int l, int n, int k0, int nk, long long plane, double *out) {
+                   mg(mgic_field_grchombo_vars_ctt(psi[l], phi ? phi[l] : nullptr, n, k0, nk, bh0,
+                                                   npunct, table, pi ? pi[l] : nullptr, pot,
+                                                   abar + 6 * l, out, 0));
+                   copy_in(K[l], n, k0, nk, plane, out + 7 * plane * nk);
+                   for (int c = 0; cons && c < 4; ++c)
+                     copy_in(cons[5 * l + c], n, k0, nk, plane, out + (27 + c) * plane * nk);
+                 });
+  });
+}
+
 MGIC_IO_API int mgic_io_write_solver_data_punct(const char *filename, int nlevels,
                                                 const mgic_field *dpsi, const mgic_field *rhs,
                                                 const mgic_field *psi, const mgic_field *phi,

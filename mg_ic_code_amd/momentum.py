@@ -393,16 +393,22 @@ class MomentumSolver:
 
 def solve_vector_potential(ms: MomentumSolver, mf: MomentumFields, psi: Sequence[LevelData],
                            bh: dict, mat: FilledMatter, punctures=None,
-                           phi: Optional[Sequence[LevelData]] = None) -> List[int]:
+                           phi: Optional[Sequence[LevelData]] = None,
+                           add_source=None) -> List[int]:
     """Steps 2-3 of an NL iteration with `momentum` on: S_i from the current
     psi and the three solves for V_i, then the right-hand side of U from V
     with its ghosts and the solve for U.  V_i and U are the initial guesses
-    and keep their values between calls.  Returns the four iteration counts."""
+    and keep their values between calls.  Returns the four iteration counts.
+    add_source: None, or a callable (level, S) that adds a further term to the
+    three S_i of that level on their valid cells, before the scaling by -beta
+    and the projection (cttk.py: the (2/3) psi^6 D_i K of a K that varies)."""
     nlev = len(ms.grids)
     comm = ms.grids[0].comm
     for l in range(nlev):
         momentum_source(psi[l], ms.rhs[l], bh, mat.potential, mat.level(l), punctures,
                         phi[l] if phi is not None else None)
+        if add_source is not None:
+            add_source(l, ms.rhs[l])
     its = ms.solve_three([[mf.V[l][i] for l in range(nlev)] for i in range(3)],
                          [[ms.rhs[l][i] for l in range(nlev)] for i in range(3)])
     for l in range(nlev):

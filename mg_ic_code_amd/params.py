@@ -7,6 +7,7 @@ N, refRatio forced to 2, one periodicity flag for all directions).
 """
 from __future__ import annotations
 
+import math
 import shlex
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
@@ -111,6 +112,17 @@ class PoissonParameters:
     # 3p); a list of [cx, cy, cz, r0], or "punctures"; absent: None, nothing of
     # it is loaded or launched
     horizons: Optional[object] = None
+    # cttk = 0|1 (not a key of the reference): 1 closes the constraints of a
+    # periodic one-level deck by the CTTK method (cttk.py): psi is
+    # chosen, K varies in space and the momentum constraint is solved with its
+    # gradient as a source; tools/run_poisson.py then runs cttk_solve in place
+    # of poisson_solve; absent: 0, nothing of it is loaded or launched.
+    # cttk_tolerance: the loop stops at max|K - K_prev| <= tolerance * max|K|
+    # (positive; absent: 1e-10); cttk_max_iterations: the momentum passes it
+    # may take (at least 1; absent: 50)
+    cttk: int = 0
+    cttk_tolerance: float = 1.0e-10
+    cttk_max_iterations: int = 50
 
     # what getPoissonParameters derives besides (PoissonParameters.cpp:68, :78-79,
     # :111-128): one more level than max_level, ratio 2 on every level, the
@@ -281,6 +293,21 @@ def read_params(text: str, overrides: Optional[Dict[str, str]] = None) -> Poisso
         p.horizons = rows
     if p.horizons is not None and p.is_periodic:
         raise ValueError("horizons are not defined on a periodic domain (is_periodic = 1)")
+    ck = get("cttk", int, required=False)
+    if ck is not None:
+        if ck not in (0, 1):
+            raise ValueError(f"cttk must be 0 or 1, got {ck}")
+        p.cttk = ck
+    ct = get("cttk_tolerance", float, required=False)
+    if ct is not None:
+        if not (ct > 0.0 and math.isfinite(ct)):
+            raise ValueError(f"cttk_tolerance must be a positive number, got {ct}")
+        p.cttk_tolerance = ct
+    cm = get("cttk_max_iterations", int, required=False)
+    if cm is not None:
+        if cm < 1:
+            raise ValueError(f"cttk_max_iterations must be at least 1, got {cm}")
+        p.cttk_max_iterations = cm
     return p
 
 

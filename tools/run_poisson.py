@@ -88,6 +88,13 @@ usage: python tools/run_poisson.py [params.txt] [--size N] [--boxes-per-rank x,y
                                    [--puncture-masses] [--target-masses "T1 T2 ..."]
                                    [--lineout "x0 y0 z0 x1 y1 z1 n"]
                                    [--horizon "cx cy cz r0"]... [--horizons-at-punctures]
+                                   [--cttk] [--cttk-tol TOL] [--cttk-max-iter N]
+
+With --cttk (or the deck's cttk = 1) a periodic one-level deck without holes is
+closed by the CTTK method (mg_ic_code_amd/cttk.py) in place of poisson_solve:
+psi = 1, K varies in space.  The momentum solves and max|K - K_prev| of every
+pass, K's range and, with --constraints, the corrected constraint norms are
+printed, and the JSON line carries them under the key "cttk".
 """
 import argparse
 import json
@@ -97,6 +104,37 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def run_cttk(args, prm, levels, matter, phi0, n, nboxes):
+    """--cttk (or the deck's cttk = 1): cttk_solve in place of poisson_solve."""
+    import mg_ic_code_amd as mg
+    t0 = time.perf_counter()
+    res = mg.cttk_solve(levels, prm, matter=matter, phi0=phi0, tol=args.cttk_tol,
+                        max_iterations=args.cttk_max_iter, constraints=args.constraints,
+                        max_depth=args.max_depth)
+    mg.device_synchronize()
+    dt = time.perf_counter() - t0
+    for i, its in enumerate(res.momentum_iterations):
+        print(f"CTTK pass {i + 1}: momentum solves V1 V2 V3 U: "
+              + " ".join(str(v) for v in its) + " BiCGStab iterations; removed means of S1 S2 S3: "
+              + " ".join(f"{m:.16e}" for m in res.momentum_net[i]))
+    for i, s in enumerate(res.k_steps):
+        print(f"CTTK pass {i + 1}: max|K - K_prev| = {s:.16e}")
+    print(f"CTTK K: max|K| = {res.k_max:.16e} mean = {res.k_mean:.16e}; "
+          f"{res.iterations} passes, converged {res.converged}")
+    if args.constraints:
+        for line in res.constraints.lines():
+            print(line)
+    out = {"n": n, "boxes": nboxes, "converged": res.converged, "seconds": round(dt, 3),
+           "cttk": {"iterations": res.iterations, "k_steps": res.k_steps, "k_max": res.k_max,
+                    "k_mean": res.k_mean},
+           "momentum_iterations": res.momentum_iterations, "momentum_net": res.momentum_net,
+           "momentum_net_relative": res.momentum_net_relative}
+    if args.constraints:
+        out["cttk"]["max_norm"] = res.constraints.max_norm
+        out["cttk"]["relative_ham"] = res.constraints.relative_ham
+    print(json.dumps(out))
 
 
 def main():
@@ -148,6 +186,15 @@ def main():
                          "radius R0; repeatable; overrides the deck's")
     ap.add_argument("--horizons-at-punctures", action="store_true",
                     help="look for a horizon about every puncture, from r0 = its bare mass")
+    ap.add_argument("--cttk", action="store_true",
+                    help="close the constraints of a periodic one-level deck by the CTTK method: "
+                         "psi = 1, K varies in space (default: the deck's cttk)")
+    ap.add_argument("--cttk-tol", type=float, default=None, metavar="TOL",
+                    help="the CTTK loop stops at max|K - K_prev| <= TOL max|K| (default: the "
+                         "deck's cttk_tolerance)")
+    ap.add_argument("--cttk-max-iter", type=int, default=None, metavar="N",
+                    help="the momentum passes the CTTK loop may take (default: the deck's "
+                         "cttk_max_iterations)")
     args = ap.parse_args()
     if args.horizon and args.horizons_at_punctures:
         ap.error("--horizon and --horizons-at-punctures exclude each other")
@@ -205,8 +252,10 @@ def main():
             levels.append(mg.Grid(grid.comm, ldom, lboxes, ldx,
                                   periodic=(1, 1, 1) if prm.is_periodic else (0, 0, 0),
                                   patches=True))
+    if args.cttk or prm.cttk:
+        return run_cttk(args, prm, levels, matter, phi0, n, len(boxes))
     from mg_ic_code_amd import sample
-    lineout_spec = sample.parse_lineout(args.lineout) if args.lineout is not None else None
+    lineout_spec =sample.parse_lineout(args.lineout) if args.lineout is not None else None
     targets = args.target_masses if args.target_masses is not None else prm.target_masses
     kwargs = dict(max_depth=args.max_depth, phi0=phi0, matter=matter,
                   constraints=args.constraints, momentum=True if args.momentum else None,
