@@ -41,6 +41,7 @@ from .constraints import (  # noqa: F401
 )
 from .cttk import CTTKError, CTTKResult, cttk_solve  # noqa: F401
 from .grids import set_grids  # noqa: F401
+from .khyb import HybridKError, set_K_from_matter  # noqa: F401
 from .horizon import (  # noqa: F401
     ExpansionResult,
     HorizonResult,

@@ -740,6 +740,47 @@ def cttk_call(name: str, *args) -> int:
     return st
 
 
+# ---- libmgic_khyb.so (include/mgic_khyb.h): K(x) from the matter's energy,
+# the hybrid CTTK choice, loaded on first use (khyb.py); missing or
+# unloadable = an ImportError, no fallback
+KHYB_LIB_PATH = os.path.join(_HERE, "libmgic_khyb.so")
+KHYB_SIGNATURES = {
+    "mgic_khyb_last_error": [],
+    "mgic_khyb_K": [H, H, H, PD, c_double, H, PLL],
+    "mgic_khyb_launch_ledger_dump": [c_char_p],
+    "mgic_khyb_launch_ledger_reset": [],
+}
+_khyb = None
+
+
+def khyb_lib() -> ctypes.CDLL:
+    global _khyb
+    if _khyb is None:
+        if not os.path.exists(KHYB_LIB_PATH):
+            raise ImportError(f"{KHYB_LIB_PATH} not found: build it with __graft_entry__.build()")
+        L = ctypes.CDLL(KHYB_LIB_PATH)
+        for name, argtypes in KHYB_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.argtypes = argtypes
+            fn.restype = c_char_p if name == "mgic_khyb_last_error" else c_int
+        _khyb = L
+    return _khyb
+
+
+def khyb_loaded() -> bool:
+    """Whether libmgic_khyb.so has been loaded by this process."""
+    return _khyb is not None
+
+
+def khyb_call(name: str, *args) -> int:
+    L = khyb_lib()
+    st = getattr(L, name)(*args)
+    if st < 0:
+        msg = L.mgic_khyb_last_error()
+        raise MgicError(name, st, msg.decode() if msg else "")
+    return st
+
+
 def last_error() -> str:
     msg = lib.mgic_last_error()
     return msg.decode() if msg else ""

@@ -47,7 +47,9 @@ switch the violation stays, as before.
 Not done here: no potential beyond this polynomial; no periodic images.
 Convergence is not guaranteed for large potentials: with constant K the
 operator's aCoef becomes indefinite when V(phi(x)) - <V> outweighs the
-gradient energy.
+gradient energy.  `poisson_solve(..., hybrid_K=True)` (khyb.py,
+DESIGN.md 3r) is the way round it on a deck that is not periodic: K(x) chosen
+so that rho drops out of m.
 """
 from __future__ import annotations
 

@@ -38,6 +38,11 @@ With reflux (the keyword, or the deck's reflux = 1) every AMRSolver of the
 solve adds the reflux term at the coarse-fine faces: the
 composite operator is then conservative, and a periodic hierarchy takes the
 projected momentum solve.
+
+With hybrid_K (the keyword, or the deck's hybrid_K = 1; khyb.py)
+a deck that is not periodic is solved by the hybrid CTTK method: K(x) is set
+from the matter's energy once before the loop, every iteration's momentum step
+carries (2/3) psi^6 D_i K in its source, and the coefficients see no matter.
 """
 from __future__ import annotations
 
@@ -52,6 +57,7 @@ from .core import (AMRMultiGrid, AMRSolver, BiCGStabSolver, Grid, LevelData, Mul
                    OperatorParams, SolverParams, defineOperatorFactory, set_nl_coefs, BH_KEYS)
 from ._lib import call
 from . import horizon as _horizon
+from . import khyb as _khyb
 from . import sample as _sample
 from .adm import adm_charges, check_base, check_hierarchy, parse_half_widths, resolve_table
 from .constraints import constraints as constraint_report
@@ -61,7 +67,7 @@ from .momentum import (MomentumFields, MomentumSolver, check_momentum_request, r
                        resolve_zero_mode, set_longitudinal, set_nl_coefs_ctt, set_nl_integrand_ctt,
                        solve_vector_potential)
 from .params import PoissonParameters
-from .phi import resolve_phi0, set_nl_coefs_phi, set_nl_integrand_phi
+from .phi import PhiProfile, resolve_phi0, set_nl_coefs_phi, set_nl_integrand_phi
 from .punctures import resolve_punctures, set_nl_coefs_punct, set_nl_integrand_punct
 
 
@@ -111,6 +117,10 @@ class NLResult:
     # poisson_solve(horizons=...): one horizon.HorizonResult per requested
     # surface, found on the returned psi (and the total tensor, with momentum=True)
     horizons: object = None
+    # poisson_solve(hybrid_K=True): the K(x) of the hybrid CTTK method (khyb.py)
+    # with its ghost layer 1 filled, a LevelData or one per AMR level, and max|K|
+    K: object = None
+    k_max: float = 0.0
 
 
 def set_nl_integrand(psi: LevelData, out: LevelData, bh: dict) -> None:
@@ -124,7 +134,9 @@ def _coefs(psi, phi, a, rhs, bh, punct=None, mat=None, lev=0, mom=None) -> None:
     deck's two holes (punct None) or the puncture table; no matter (mat None:
     today's calls) or the filled matter's potential and its Pi_0 of level lev;
     mom (with matter): A2 of the total tensor, the momentum fields' LW_ij of
-    level lev added to the Bowen-York one."""
+    level lev added to the Bowen-York one.  mat is what m reads, which need not
+    be the matter of the momentum source: the hybrid CTTK solve hands over a
+    zero potential without a Pi_0 (khyb.HybridK.no_matter)."""
     if mom is not None:
         set_nl_coefs_ctt(psi, a, rhs, bh, mat.potential, mom.lw(lev), mat.level(lev), punct, phi)
     elif mat is not None:
@@ -157,7 +169,8 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
                   matter=None, constraints: bool = False,
                   momentum: Optional[bool] = None,
                   zero_mode: Optional[str] = None, reflux=None, adm=None,
-                  puncture_masses: Optional[bool] = None, horizons=None) -> NLResult:
+                  puncture_masses: Optional[bool] = None, horizons=None,
+                  hybrid_K: Optional[bool] = None) -> NLResult:
     """phi0: None -- the analytic Gaussian, evaluated in the kernels; else a
     phi.PhiProfile, or one pre-filled LevelData per level: phi_0 is stored once
     before the NL loop (set_initial_conditions, SetLevelData.cpp:32-71) and the
@@ -218,7 +231,29 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
     solve itself and the output files are unchanged.  A periodic deck and a bad
     centre or radius are a ValueError before anything is stored or launched.
     None: the deck's horizons; absent there too: nothing of it is loaded or
+    launched.
+    hybrid_K: True -- the hybrid CTTK method (khyb.py): K varies
+    in space, K = -sqrt(24 pi G (Pi_0^2/2 + V(phi_0))), so that the matter's
+    energy drops out of the psi equation, and every NL iteration's momentum
+    step carries (2/3) psi^6 D_i K in its source.  phi_0 is stored (phi0 None:
+    the deck's Gaussian as PhiProfile.gaussian() stores it), K is evaluated
+    once before the loop (HybridKError where rho < 0) and attached as
+    NLResult.K with NLResult.k_max; the constraint report and the final data
+    carry K's terms and K itself.  It implies momentum=True and needs what that
+    needs (MatterArgumentError otherwise); a periodic deck (cttk_solve is that
+    path), an explicit momentum=False, and adm or horizons (both assume
+    K = 0) are a ValueError before anything is stored, loaded or launched.
+    None: the deck's hybrid_K; absent or 0 there: nothing of it is loaded or
     launched."""
+    hybrid_K = _khyb.resolve_hybrid_K(hybrid_K, prm)
+    if hybrid_K:  # refused before anything is stored, loaded or launched
+        _khyb.check_hybrid_request(
+            prm, resolve_matter(matter, prm), momentum,
+            adm if adm is not None else getattr(prm, "adm_half_widths", None),
+            horizons if horizons is not None else getattr(prm, "horizons", None))
+        momentum = True
+        if phi0 is None:
+            phi0 = PhiProfile.gaussian()
     if horizons is None:
         horizons = getattr(prm, "horizons", None)
     if horizons is not None:  # refused before anything is stored or launched
@@ -252,7 +287,7 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
             return _poisson_solve_amr(list(grid), prm, max_depth, prolong_type, bottom_solver,
                                       max_NL_iterations, output_dir, phi0, punct, matter,
                                       constraints, momentum, zero_mode, reflux, adm,
-                                      bool(puncture_masses), horizons)
+                                      bool(puncture_masses), horizons, hybrid_K)
         grid = grid[0]
     mat = fill_matter(matter, [grid], prm)
     phis = resolve_phi0(phi0, [grid], prm)
@@ -280,6 +315,12 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
             max_depth=depth, n_pre=prm.numMGsmooth, n_post=prm.numMGsmooth,
             n_bottom=prm.numMGsmooth, bottom_solver=bottom_solver,
             agglomerate_below=32 if grid.comm.size > 1 else 0), zero_mode)
+    hyb = extra = None
+    coef_mat = mat
+    if hybrid_K:  # K does not depend on psi: once, before the loop
+        hyb = _khyb.HybridK([grid], mat, phis, prm.G_Newton)
+        res.K, res.k_max = hyb.K[0], msolve.ops[0].norm(hyb.K[0], 0)
+        extra, coef_mat = hyb.source([psi]), hyb.no_matter
     n_nl = prm.max_NL_iterations if max_NL_iterations is None else max_NL_iterations
     dx = grid.dx
     ones = integrand = None
@@ -302,8 +343,8 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
             bh["constant_K"] = -math.sqrt(abs(integral) / volume)
             res.constant_K.append(bh["constant_K"])
         if momentum and not periodic:
-            _momentum_step(res, msolve, mom, [psi], bh, mat, punct, phis)
-        _coefs(psi, phi, a, rhs, bh, punct, mat, 0, mom)  # :155-161
+            _momentum_step(res, msolve, mom, [psi], bh, mat, punct, phis, extra)
+        _coefs(psi, phi, a, rhs, bh, punct, coef_mat, 0, mom)  # :155-161
         fac = defineOperatorFactory(grid, a, b, op_params)
         # N > 1: depths whose boxes are below 32 cells a side are gathered to
         # one box on rank 0 (the coarsest levels solved on rank 0)
@@ -328,13 +369,16 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
             res.converged = nrm < prm.tolerance
             break
     write = None
-    if output_dir is not None:  # :227-230
+    if output_dir is not None and hyb is None:  # :227-230
         def write():
             output_final_data([psi], bh, prm.max_level, [2],
                               os.path.join(output_dir, "vcPoissonFinal.3d.hdf5"), phi=phis,
                               punctures=punct, matter=mat, constraints=constraints, momentum=mom)
     finish_nl_loop(res, write)
-    if constraints:
+    if hyb is not None:
+        _finish_hybrid(res, hyb, [psi], bh, phis, punct, mat, mom, constraints, output_dir,
+                       prm.max_level, [2])
+    elif constraints:
         res.constraints = constraint_report(
             psi, bh, phis, punct, mat, momentum=mom,
             momentum_net=res.momentum_net[-1] if res.momentum_net else None)
@@ -347,11 +391,29 @@ def poisson_solve(grid, prm: PoissonParameters, max_depth: int = -1,
     return res
 
 
-def _momentum_step(res: NLResult, msolve, mom, psi, bh, mat, punct, phis) -> None:
+def _finish_hybrid(res: NLResult, hyb, psi, bh, phis, punct, mat, mom, constraints: bool,
+                   output_dir: Optional[str], max_level: int, refs, reflux: bool = False) -> None:
+    """After a hybrid CTTK loop that did not diverge: the constraint report
+    with K's terms (bh["constant_K"] stays 0), then the final data with K from
+    the field and, with the report, components 27-30 from its corrected
+    fields."""
+    rep = None
+    if constraints:
+        rep = res.constraints = constraint_report(
+            psi if len(psi) > 1 else psi[0], bh, phis, punct, mat, momentum=mom, reflux=reflux,
+            correct=hyb.correct)
+    if output_dir is not None:
+        _khyb.write_final_data(os.path.join(output_dir, "vcPoissonFinal.3d.hdf5"), psi, hyb.K, bh,
+                               mat, mom, phis, punct, rep.fields if rep is not None else None,
+                               max_level, refs)
+
+
+def _momentum_step(res: NLResult, msolve, mom, psi, bh, mat, punct, phis, add_source=None) -> None:
     """V_i and U at the current psi (one LevelData per level), then LW_ij of the
-    total tensor; with the zero mode projected, the means removed from S_i."""
+    total tensor; with the zero mode projected, the means removed from S_i.
+    add_source: solve_vector_potential's."""
     res.momentum_iterations.append(
-        solve_vector_potential(msolve, mom, psi, bh, mat, punct, phis))
+        solve_vector_potential(msolve, mom, psi, bh, mat, punct, phis, add_source=add_source))
     set_longitudinal(msolve, mom)
     res.momentum_residuals.append(list(msolve.final_norms))
     msolve.final_norms.clear()
@@ -376,7 +438,8 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
                        matter=None, constraints: bool = False,
                        momentum: bool = False, zero_mode: str = "refuse",
                        reflux: bool = False, adm=None,
-                       puncture_masses: bool = False, horizons=None) -> NLResult:
+                       puncture_masses: bool = False, horizons=None,
+                       hybrid_K: bool = False) -> NLResult:
     """poissonSolve over nlevels = len(grids) AMR levels (Main_PoissonSolver.cpp:51-250)."""
     periodic = bool(prm.is_periodic)
     if periodic != all(grids[0].periodic):
@@ -405,6 +468,12 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
     if momentum:
         mom = res.momentum = MomentumFields(grids)
         msolve = MomentumSolver(grids, prm, op_params, sp, zero_mode, reflux=reflux)
+    hyb = extra = None
+    coef_mat = mat
+    if hybrid_K:  # K does not depend on psi: once, before the loop
+        hyb = _khyb.HybridK(grids, mat, phis, prm.G_Newton, msolve.amr)
+        res.K, res.k_max = hyb.K, msolve.amr.norm(hyb.K, 0)
+        extra, coef_mat = hyb.source(psi), hyb.no_matter
     n_nl = prm.max_NL_iterations if max_NL_iterations is None else max_NL_iterations
     volume = prm.domainLength[0] * prm.domainLength[1] * prm.domainLength[2]
     integrand = geom = None
@@ -427,10 +496,10 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
             res.constant_K.append(bh["constant_K"])
         if momentum and not periodic:  # V_i and U at the current psi, then LW_ij
             res.momentum_iterations.append(
-                solve_vector_potential(msolve, mom, psi, bh, mat, punct, phis))
+                solve_vector_potential(msolve, mom, psi, bh, mat, punct, phis, add_source=extra))
             set_longitudinal(msolve, mom)
         for l in range(nlev):  # :154-160
-            _coefs(psi[l], phi[l], a[l], rhs[l], bh, punct, mat, l, mom)
+            _coefs(psi[l], phi[l], a[l], rhs[l], bh, punct, coef_mat, l, mom)
         amr = AMRSolver(list(zip(grids, a, b)), op_params, sp, reflux=reflux)  # :163-170
         solver = BiCGStabSolver(MultilevelLinearOp(amr, prm.numMGIterations),
                                 tolerance=prm.tolerance, max_iterations=prm.max_iterations,
@@ -450,13 +519,16 @@ def _poisson_solve_amr(grids: List[Grid], prm: PoissonParameters, max_depth: int
             res.converged = nrm < prm.tolerance
             break
     write = None
-    if output_dir is not None:  # :227-230
+    if output_dir is not None and hyb is None:  # :227-230
         def write():
             output_final_data(psi, bh, nlev - 1, refs,
                               os.path.join(output_dir, "vcPoissonFinal.3d.hdf5"), phi=phis,
                               punctures=punct, matter=mat, constraints=constraints, momentum=mom)
     finish_nl_loop(res, write)
-    if constraints:
+    if hyb is not None:
+        _finish_hybrid(res, hyb, psi, bh, phis, punct, mat, mom, constraints, output_dir,
+                       nlev - 1, refs, reflux)
+    elif constraints:
         res.constraints = constraint_report(
             psi, bh, phis, punct, mat, momentum=mom,
             momentum_net=res.momentum_net[-1] if res.momentum_net else None, reflux=reflux)

@@ -123,6 +123,12 @@ class PoissonParameters:
     cttk: int = 0
     cttk_tolerance: float = 1.0e-10
     cttk_max_iterations: int = 50
+    # hybrid_K = 0|1 (not a key of the reference): 1 solves a deck that is not
+    # periodic by the hybrid CTTK method (khyb.py): K varies in
+    # space so that the matter's energy drops out of the Hamiltonian
+    # constraint, and the momentum constraint is solved with its gradient as a
+    # source; absent: 0, nothing of it is loaded or launched
+    hybrid_K: int = 0
 
     # what getPoissonParameters derives besides (PoissonParameters.cpp:68, :78-79,
     # :111-128): one more level than max_level, ratio 2 on every level, the
@@ -308,6 +314,11 @@ def read_params(text: str, overrides: Optional[Dict[str, str]] = None) -> Poisso
         if cm < 1:
             raise ValueError(f"cttk_max_iterations must be at least 1, got {cm}")
         p.cttk_max_iterations = cm
+    hk = get("hybrid_K", int, required=False)
+    if hk is not None:
+        if hk not in (0, 1):
+            raise ValueError(f"hybrid_K must be 0 or 1, got {hk}")
+        p.hybrid_K = hk
     return p
 
 

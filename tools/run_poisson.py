@@ -88,13 +88,20 @@ usage: python tools/run_poisson.py [params.txt] [--size N] [--boxes-per-rank x,y
                                    [--puncture-masses] [--target-masses "T1 T2 ..."]
                                    [--lineout "x0 y0 z0 x1 y1 z1 n"]
                                    [--horizon "cx cy cz r0"]... [--horizons-at-punctures]
-                                   [--cttk] [--cttk-tol TOL] [--cttk-max-iter N]
+                                   [--cttk] [--cttk-tol TOL] [--cttk-max-iter N] [--hybrid-K]
 
 With --cttk (or the deck's cttk = 1) a periodic one-level deck without holes is
 closed by the CTTK method (mg_ic_code_amd/cttk.py) in place of poisson_solve:
 psi = 1, K varies in space.  The momentum solves and max|K - K_prev| of every
 pass, K's range and, with --constraints, the corrected constraint norms are
 printed, and the JSON line carries them under the key "cttk".
+
+With --hybrid-K (or the deck's hybrid_K = 1) a deck that is not periodic, holes
+or none, is solved by the hybrid CTTK method (mg_ic_code_amd/khyb.py): K varies
+in space so that the matter's energy drops out of the psi equation, and the
+momentum solve carries its gradient.  It implies --momentum.  max|K| and, with
+--constraints, the corrected constraint norms are printed, and the JSON line
+carries them under the key "hybrid_K".
 """
 import argparse
 import json
@@ -195,6 +202,9 @@ def main():
     ap.add_argument("--cttk-max-iter", type=int, default=None, metavar="N",
                     help="the momentum passes the CTTK loop may take (default: the deck's "
                          "cttk_max_iterations)")
+    ap.add_argument("--hybrid-K", dest="hybrid_K", action="store_true",
+                    help="solve a deck that is not periodic by the hybrid CTTK method: K(x) from "
+                         "the matter's energy (default: the deck's hybrid_K); implies --momentum")
     args = ap.parse_args()
     if args.horizon and args.horizons_at_punctures:
         ap.error("--horizon and --horizons-at-punctures exclude each other")
@@ -261,7 +271,8 @@ def main():
                   constraints=args.constraints, momentum=True if args.momentum else None,
                   zero_mode=args.momentum_zero_mode, reflux=True if args.reflux else None,
                   adm=args.adm,
-                  horizons="punctures" if args.horizons_at_punctures else args.horizon)
+                  horizons="punctures" if args.horizons_at_punctures else args.horizon,
+                  hybrid_K=True if args.hybrid_K else None)
     t0 = time.perf_counter()
     msolve = None
     if targets is not None:
@@ -280,6 +291,8 @@ def main():
               + ("; removed means of S1 S2 S3: "
                  + " ".join(f"{m:.16e}" for m in res.momentum_net[i])
                  if res.momentum_net else ""))
+    if res.K is not None:
+        print(f"hybrid K: max|K| = {res.k_max:.16e}")
     if args.constraints:
         for line in res.constraints.lines():
             print(line)
@@ -319,6 +332,11 @@ def main():
         out["constant_K"] = res.constant_K
     if res.momentum is not None:
         out["momentum_iterations"] = res.momentum_iterations
+    if res.K is not None:
+        out["hybrid_K"] = {"k_max": res.k_max}
+        if args.constraints:
+            out["hybrid_K"]["max_norm"] = res.constraints.max_norm
+            out["hybrid_K"]["relative_ham"] = res.constraints.relative_ham
     if res.momentum_net:
         out["momentum_net"] = res.momentum_net
         out["momentum_net_relative"] = res.momentum_net_relative
